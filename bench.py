@@ -2,8 +2,15 @@
 """bench.py — BASELINE.json headline: factor stock-days/s (whole node) + % of HBM roofline
 on 5,000 stocks x 240 min x 2,500 days.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run sets up the panel, warms up, times the K steps and prints the result line
+(cpu_baseline null, extras empty, roofline.kernels null).  --full adds everything else
+described below: the CPU baseline, the extras (stage 2 / 3, ingest, end-to-end, null
+path, rank share, c5), the per-kernel times and, at N > 1, the per-collective accounting
+pass; --no-cpu-baseline / --no-extras / --kernel-times / --null-only trim a --full run.
+--dump-outputs DIR writes what the last timed step returned (dump_outputs below).
 
 Step = one pass of stage 1 (all 58 CICC factors, including the doc_pdf frame-wide rank
 and its cross-rank exchange) over the whole panel, inputs already resident in HBM.
@@ -502,6 +509,57 @@ def final_exposure_extras(val, state, days: int = 250, name: str = "vol_return1m
             "final_exposure_phases_s": {k: round(v, 4) for k, v in ph.items()}}
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # all files of one rank together
+DUMP_SEED = 20251101
+
+
+def dump_outputs(path: str, out, s0: int, rank: int, world: int):
+    """What engine.compute_factors returned in the last timed step, as .npy files in `path`.
+
+    The pass returns (val f64 [58][D][S_loc], state u8 [58][D][S_loc], ids); at c4 that is
+    5.8 GB of values, so a fixed sample of stock-days is kept: n (day, stock) positions of
+    the rank's shard, drawn without replacement by numpy PCG64(DUMP_SEED) and sorted (all
+    of them where the whole output fits the budget), every factor of each.  The panel is
+    seeded (synth.make_panel_device), so the same arguments give the same positions and
+    the same inputs from run to run.  Files (suffix _rank<r> at N > 1):
+      val.npy          float64 [58][n]  the finite values; 0.0 where state is not VALUE (2)
+                                        (the engine leaves those cells of val unwritten)
+                                        and where the value is NaN or +-inf (a value the
+                                        reference computes too, e.g. a correlation of a
+                                        constant series): every file holds finite numbers
+      nonfinite.npy    float32 [58][n]  0 finite or no value, 1 NaN, 2 +inf, 3 -inf
+      state.npy        float32 [58][n]  0 absent, 1 null, 2 value
+      factor_ids.npy   float64 [58]     catalog ids of the rows
+      sample_day.npy   float64 [n]      day index of each position
+      sample_stock.npy float64 [n]      stock index of each position (of the whole panel)"""
+    import torch
+    from mff import engine
+
+    val, state, ids = out
+    nf, D, S_loc = val.shape
+    total = D * S_loc
+    n = min(total, (DUMP_BUDGET_BYTES - nf * 8) // (nf * (8 + 4 + 4) + 2 * 8))
+    if n < total:
+        pos = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(total, n, replace=False))
+    else:
+        pos = np.arange(total)
+    idx = torch.from_numpy(pos.astype(np.int64)).to(val.device)
+    s = state.reshape(nf, total)[:, idx]
+    v = val.reshape(nf, total)[:, idx]
+    v = torch.where(s == engine.VALUE, v, torch.zeros_like(v))
+    kind = torch.where(torch.isnan(v), 1.0, torch.where(torch.isinf(v), torch.where(v > 0, 2.0, 3.0), 0.0))
+    v = torch.where(kind == 0, v, torch.zeros_like(v))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("val", v.cpu().numpy()),
+                    ("nonfinite", kind.cpu().numpy().astype(np.float32)),
+                    ("state", s.cpu().numpy().astype(np.float32)),
+                    ("factor_ids", np.asarray(ids, dtype=np.float64)),
+                    ("sample_day", (pos // S_loc).astype(np.float64)),
+                    ("sample_stock", (pos % S_loc + s0).astype(np.float64))):
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -519,7 +577,16 @@ def main():
     ap.add_argument("--ingest-host-days", type=int, default=4)
     ap.add_argument("--e2e-days", type=int, default=8)
     ap.add_argument("--null-only", action="store_true", help="with --no-extras: still run the null-path extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the extras, the per-kernel times and (N > 1) the "
+                         "per-collective accounting pass; off: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        if args.kernel_times or args.null_only:
+            ap.error("--kernel-times and --null-only measure beyond the timed steps: add --full")
+        args.no_cpu_baseline = args.no_extras = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -555,8 +622,11 @@ def main():
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
            for _ in range(args.steps)]
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
         out = step(evs[k])
+        if args.dump_outputs and k == args.steps - 1:
+            last = out  # the last timed step's outputs, written after the timing
         del out
     torch.cuda.synchronize()
     if comm is not None:
@@ -566,10 +636,13 @@ def main():
     if comm is not None:
         comm.all_reduce_max(el)
     elapsed = float(el.item())
+    if last is not None:
+        dump_outputs(args.dump_outputs, last, s0, rank, world)
+        del last
 
     k_ms = sum(a.elapsed_time(b) for a, b in evs) / max(1, len(evs))
     exchange = None
-    if comm is not None and hasattr(comm, "stats"):
+    if args.full and comm is not None and hasattr(comm, "stats"):
         # one more (untimed) pass with every collective accounted: bytes this rank sends
         # and device ms between events around each call (doc_pdf exchange)
         comm.stats = dist.CommStats()
