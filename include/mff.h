@@ -321,6 +321,45 @@ int mff_xs_rank(const double* val, const uint8_t* state, int rows, int D, int S_
                 double* out_val, uint8_t* out_state, void* workspace, void* stream);
 
 /*
+ * Cross-sectional preprocessing ahead of the IC / group tests: per-day MAD winsorisation,
+ * industry / size neutralisation and standardisation of exposure rows [rows][D][S].  No
+ * reference function (the reference tests raw exposures, Factor.py:127-350); this is the
+ * build's definition.  One segment = one row on one day, over its S stocks.
+ *   group int32 [D][S]: industry id in [0, G), anything else (-1) = none; NULL = no
+ *     industries (one group: intercept only).  G <= max_groups().
+ *   size / size_state [D][S]: the size covariate itself (normally ln market cap) and its
+ *     state; NULL = no covariate.
+ *   Usable set U: state VALUE and x finite; an industry, when group is given; size_state
+ *     VALUE and size finite, when size is given.  n = |U|.
+ *   1. winsor_k > 0: med = median of x over U (numpy.median: the mean of the two middle
+ *      order statistics for even n), mad = median of |x - med|; mad > 0: x clipped to
+ *      med -+ winsor_k * 1.4826 * mad; mad == 0: no clipping.
+ *   2. e = the OLS residual of x on industry dummies + size by within-industry demeaning:
+ *      x~ = x - mean_g(x), z~ = z - mean_g(z) over the industry's members of U,
+ *      beta = sum(x~ z~) / sum(z~ z~) (0 when the denominator is 0), e = x~ - beta z~
+ *      (e = x~ without a covariate).
+ *   3. standardize != 0: e <- (e - mean(e)) / sd(e), ddof = 1.
+ *   Degrees of freedom: k = non-empty industries among U (+ 1 with a covariate);
+ *   n - k < 1, or n < 2 when standardising: every stock of U gets NULL.
+ *   States: ABSENT stays ABSENT, NULL stays NULL, a VALUE NaN / +-inf passes through
+ *   unchanged, a finite VALUE without industry or size becomes NULL, U gets VALUE (or NULL
+ *   by the rule above).  The result is bit-identical from run to run (fixed summation
+ *   orders, no floating-point atomics).
+ * workspace: mff_xs_neutralize_workspace_bytes(D, S) bytes of device scratch, required
+ * when group is given (the per-day industry order, built by the call itself).
+ * Errors (negative, nothing launched): S > max_stocks(), G outside [1, max_groups()] with
+ * group given, a negative size, size without size_state.
+ */
+int mff_xs_neutralize_max_stocks(void); /* 8192 */
+int mff_xs_neutralize_max_groups(void); /* 256 */
+size_t mff_xs_neutralize_workspace_bytes(int D, int S);
+int mff_xs_neutralize(const double* val, const uint8_t* state, int rows, int D, int S,
+                      const int32_t* group /* [D][S], -1 = none; NULL = no industries */, int G,
+                      const double* size, const uint8_t* size_state /* [D][S]; NULL = no covariate */,
+                      double winsor_k /* <= 0: off */, int standardize,
+                      double* out_val, uint8_t* out_state, void* workspace, void* stream);
+
+/*
  * Factor IC / rank-IC test.  Replaces Factor.ic_test
  * (Factor.py:127-229).  Inputs are dense [D][S] (val, state) like stage 1's output rows.
  * mff_future_return: Factor.py:142-162 — per stock over its present days,

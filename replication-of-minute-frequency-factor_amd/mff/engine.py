@@ -10,6 +10,7 @@ Stage map:
   :func:`compute_factors`  stage 1, the 58 cal_* of MinuteFrequentFactorCalculateMethodsCICC.py
   :func:`rolling`          stage 2, MinFreqFactor.cal_final_exposure(mode='days') (MF:187-240)
   :func:`cross_section`    stage 3, per-day z-score / average rank
+  :func:`neutralize`       per-day MAD winsorise, industry / size neutralise, standardise
 """
 from __future__ import annotations
 
@@ -892,6 +893,104 @@ def xs_rank_sharded(comm, val: torch.Tensor, state: torch.Tensor, S_all: int, ra
         out_v[:, a:b] = gv[q, :, :b - a, :S_loc]
         out_s[:, a:b] = gs[q, :, :b - a, :S_loc]
     return out_v, out_s
+
+
+NEUTRALIZE_MAX_GROUPS = 256  # mff_xs_neutralize_max_groups()
+
+
+def _neutralize_local(lib, val, state, group, G, size_val, size_state, winsor, standardize):
+    """mff_xs_neutralize on whole days held by one rank."""
+    rows, D, S = val.shape
+    dev = val.device
+    ov = torch.empty_like(val)
+    os_ = torch.empty_like(state)
+    ws = None
+    if group is not None:
+        ws = torch.empty(max(lib.mff_xs_neutralize_workspace_bytes(D, S), 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mff_xs_neutralize(_lib.ptr(val), _lib.ptr(state), rows, D, S, _lib.ptr(group), int(G or 0),
+                                     _lib.ptr(size_val), _lib.ptr(size_state), float(winsor), int(bool(standardize)),
+                                     _lib.ptr(ov), _lib.ptr(os_), _lib.ptr(ws), _stream(dev)), "mff_xs_neutralize")
+    return ov, os_
+
+
+def neutralize(val: torch.Tensor, state: torch.Tensor, group: Optional[torch.Tensor] = None,
+               size_val: Optional[torch.Tensor] = None, size_state: Optional[torch.Tensor] = None, *,
+               G: Optional[int] = None, winsor: float = 3.0, standardize: bool = True, comm=None,
+               stocks_total: Optional[int] = None):
+    """Per-day MAD winsorisation, industry / size neutralisation and standardisation of
+    exposure rows [rows][D][S_loc] (mff_xs_neutralize; the definition is on its declaration
+    in include/mff.h).  ``group``: int32 [D][S_loc] industry ids in [0, G), -1 = none (None:
+    no industries); ``G``: the number of industries (None: the largest id + 1, agreed over
+    the ranks); ``size_val`` / ``size_state``: the size covariate [D][S_loc] (None: no
+    covariate); ``winsor`` <= 0 turns the clipping off.
+
+    Stock-sharded (``comm``): medians need whole days, so the columns travel to day owners
+    through :func:`xs_rank_sharded`'s exchange with the side inputs as two extra rows (the
+    size with its state; the industry id as an exactly representable float64, ABSENT where
+    there is none), and each owner runs the one-rank kernel on its days.
+    Returns (out_val, out_state) [rows][D][S_loc]."""
+    lib = _lib.load()
+    if val.dim() != 3 or state.shape != val.shape:
+        raise ValueError("val and state must be [rows][D][S]")
+    rows, D, S = val.shape
+    dev = val.device
+    if (size_val is None) != (size_state is None):
+        raise ValueError("size_val and size_state go together")
+    for name, t in (("group", group), ("size_val", size_val), ("size_state", size_state)):
+        if t is not None and tuple(t.shape) != (D, S):
+            raise ValueError(f"{name} must be [D][S] = [{D}][{S}], got {tuple(t.shape)}")
+    val, state = val.contiguous(), state.contiguous()
+    if group is not None:
+        group = group.to(torch.int32).contiguous()
+        if G is None:
+            G = int(group.max().item()) + 1 if group.numel() else 1
+            if comm is not None:
+                G = _agreed_max(comm, G, dev)
+            G = max(G, 1)
+        if G > lib.mff_xs_neutralize_max_groups():
+            raise _lib.MffError(f"neutralize: {G} industries above the kernel's "
+                                f"{lib.mff_xs_neutralize_max_groups()}")
+    if size_val is not None:
+        size_val = size_val.to(torch.float64).contiguous()
+        size_state = size_state.to(torch.uint8).contiguous()
+    if comm is None:
+        return _neutralize_local(lib, val, state, group, G, size_val, size_state, winsor, standardize)
+    R = comm.world_size
+    S_all = shard_width(comm, S, stocks_total, dev)
+    if R * S_all > lib.mff_xs_neutralize_max_stocks():
+        raise _lib.MffError(f"neutralize: {R} shards of up to {S_all} stocks make days of {R * S_all} columns, "
+                            f"above the kernel's {lib.mff_xs_neutralize_max_stocks()}")
+    extra_v, extra_s = [], []
+    if size_val is not None:
+        extra_v.append(size_val)
+        extra_s.append(size_state)
+    if group is not None:
+        has = group >= 0
+        extra_v.append(torch.where(has, group.to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev)))
+        extra_s.append(torch.where(has, VALUE, ABSENT).to(torch.uint8))
+    ne = len(extra_v)
+    xv = torch.cat([val] + [e[None] for e in extra_v]) if ne else val
+    xs_ = torch.cat([state] + [e[None] for e in extra_s]) if ne else state
+
+    def owner_days(v, s_, o, os2):
+        """v, s_: [rows + ne][nd][R * S_all], the owner's days whole."""
+        k = rows
+        zv = zs = gd = None
+        if size_val is not None:
+            zv, zs = v[k].contiguous(), s_[k].contiguous()
+            k += 1
+        if group is not None:
+            gd = torch.where(s_[k] == VALUE, v[k].to(torch.int32),
+                             torch.full((), -1, dtype=torch.int32, device=dev)).contiguous()
+        rv, rs = _neutralize_local(lib, v[:rows].contiguous(), s_[:rows].contiguous(), gd, G, zv, zs, winsor,
+                                   standardize)
+        o.zero_()
+        os2.fill_(ABSENT)
+        o[:rows] = rv
+        os2[:rows] = rs
+
+    ov, os_ = xs_rank_sharded(comm, xv, xs_, S_all, owner_days)
+    return ov[:rows].contiguous(), os_[:rows].contiguous()
 
 
 def future_return(pct_val: torch.Tensor, pct_state: torch.Tensor, N: int):

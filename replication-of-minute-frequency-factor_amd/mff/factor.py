@@ -232,6 +232,77 @@ class Factor:
                 plt.show()
         return group_df if return_df else None
 
+    def neutralize(self, industry=None, size: Literal["cmc", "tmc", None] = "cmc", winsor: float = 3.0,
+                   standardize: bool = True, pv_data=None, device=None) -> "Factor":
+        """Per-date preprocessing ahead of ic_test / group_test, on the GPU
+        (mff_xs_neutralize, include/mff.h): MAD winsorisation (``winsor`` x 1.4826 x MAD
+        around the median; <= 0: off), OLS residual on industry dummies and ln(market cap),
+        z-score (ddof=1).  No reference counterpart: Factor.py tests raw exposures.
+
+        ``industry``: None, or a long frame [code, industry] (one label per code) or
+        [code, date, industry]; labels of any hashable dtype, a null label = no industry.
+        ``size``: 'cmc', 'tmc' or None, read from ``pv_data`` (default: the daily
+        price-volume file); a null, non-finite or <= 0 cap is a missing covariate.
+        A stock-day with a finite exposure but no industry or no covariate comes out null.
+
+        Returns a new object of the same class named ``f"{factor_name}_neu"`` whose
+        factor_exposure holds [code, date, <that name>]; this object is left untouched."""
+        import torch
+
+        from . import engine
+        from .factors import _device
+
+        pd = _pd()
+        if size not in (None, "tmc", "cmc"):
+            raise ValueError(f"size must be 'tmc', 'cmc' or None, got {size!r}")
+        if isinstance(winsor, bool) or not isinstance(winsor, (int, float)) or np.isnan(winsor):
+            raise ValueError(f"winsor must be a number (<= 0: no winsorisation), got {winsor!r}")
+        ex = self.factor_exposure
+        codes, dates = frames.universe(ex)
+        D, S = len(dates), len(codes)
+        grp, G = None, None
+        if industry is not None:
+            cols = list(getattr(industry, "columns", []))
+            if "code" not in cols or "industry" not in cols:
+                raise ValueError("industry must be a frame with columns [code, industry] or "
+                                 "[code, date, industry]")
+            ids, labels = pd.factorize(industry["industry"])  # a null label: -1
+            G = max(len(labels), 1)
+            if G > engine.NEUTRALIZE_MAX_GROUPS:
+                raise ValueError(f"industry holds {G} distinct labels, more than the "
+                                 f"{engine.NEUTRALIZE_MAX_GROUPS} the kernel takes")
+            ids = np.asarray(ids, dtype=np.int64)
+            code_pos = pd.Index(codes).get_indexer(industry["code"].astype(str))
+            grp = np.full((D, S), -1, dtype=np.int32)
+            if "date" in cols:
+                day_pos = pd.Index(dates).get_indexer([frames._as_date(d) for d in industry["date"]])
+                ok = (code_pos >= 0) & (day_pos >= 0)
+                grp[day_pos[ok], code_pos[ok]] = ids[ok]
+            else:
+                ok = code_pos >= 0
+                if len(np.unique(code_pos[ok])) != int(ok.sum()):
+                    raise ValueError("industry without a date column must hold one row per code")
+                grp[:, code_pos[ok]] = ids[ok][None, :]
+        dev = _device(device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        zv = zs = None
+        if size is not None:
+            pv = pv_data if pv_data is not None else self._read_daily_pv_data(["code", "date", size])
+            if size not in pv.columns:
+                raise ValueError(f"pv_data has no column {size!r}")
+            pv = pv[frames.rows_in(pv, codes, dates)]
+            c_v, c_s, _, _ = frames.from_long(pv, size, codes=codes, dates=dates)
+            cap, cst = t(c_v), t(c_s)
+            ok = (cst == engine.VALUE) & torch.isfinite(cap) & (cap > 0)
+            zv = torch.where(ok, torch.log(torch.where(ok, cap, torch.ones_like(cap))), torch.zeros_like(cap))
+            zs = torch.where(ok, cst, torch.where(cst == engine.ABSENT, cst, torch.full_like(cst, engine.NULL)))
+        xv, xs, _, _ = frames.from_long(ex, self.factor_name, codes=codes, dates=dates)
+        ov, os_ = engine.neutralize(t(xv[None]), t(xs[None]), None if grp is None else t(grp), zv, zs, G=G,
+                                    winsor=float(winsor), standardize=bool(standardize))
+        torch.cuda.synchronize(dev)
+        name = f"{self.factor_name}_neu"
+        return type(self)(name, frames.to_long(ov[0].cpu().numpy(), os_[0].cpu().numpy(), codes, dates, name))
+
 
 def rebalance_periods(dates, frequency: str):
     """group_by_dynamic(every=1w/1mo/1q/1y, label='right') windows (Factor.py:249-256,
