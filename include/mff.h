@@ -360,6 +360,59 @@ int mff_xs_neutralize(const double* val, const uint8_t* state, int rows, int D, 
                       double* out_val, uint8_t* out_state, void* workspace, void* stream);
 
 /*
+ * Pairwise factor correlation: per day the rows x rows matrix of the cross-sectional
+ * correlations of exposure rows [rows][D][S] (rows = F factors), and its mean over days.
+ * No reference function (Factor.py never relates two factors); this is the build's
+ * definition, restated in numpy by tests/xs_corr_ref.py.
+ *   Usable entry u_i[d][s]: state VALUE and x finite (the usable set of mff_xs_neutralize;
+ *     NaN and +-inf drop out of the pair like a null).
+ *   Pair set P_ij(d) = {s : u_i and u_j}, n_ij = |P_ij|.
+ *   corr_ij(d) = the Pearson correlation of (x_i, x_j) over P_ij(d), both means taken over
+ *     P_ij(d) (pairwise-complete, as pandas.DataFrame.corr); NaN when n_ij < min_pairs
+ *     (min_pairs >= 2) or when either side is constant on the pair set.
+ *   Constant rule: with y = x - c_i, c_i the row's centre of that day (below), side i is
+ *     constant on P_ij when var_i|j <= 1e-12 * Q_ij, Q_ij = sum_P y_i^2,
+ *     var_i|j = Q_ij - (sum_P y_i)^2 / n_ij.  It catches an exactly constant pair set (whose
+ *     one-pass variance is rounding residue, not 0); a non-constant one reaches it only when
+ *     its spread is 1e-6 of its offset from the row mean, which f64 sums cannot resolve.
+ *   The diagonal is exactly 1.0 where defined (NaN when n_ii < min_pairs or the row is
+ *   constant), the matrix is bitwise symmetric (i <= j computed, then mirrored), values are
+ *   clamped to [-1, 1], n (int32) is always written and exact, and the result is
+ *   bit-identical from run to run (fixed summation orders, no floating-point atomics).
+ *   Spearman = the same on rows replaced per day by their average ranks over their own
+ *   usable set (mff_xs_rank after non-finite values are masked to NULL); the ranks are not
+ *   recomputed inside each pair set.
+ *   Numerics: no raw sum x, sum x^2.  Every row is centred per day by c_i(d), a value close
+ *   to its mean over its usable set (the correlation is shift-invariant: any finite centre
+ *   common to all shards gives the same result up to rounding); with m the 0/1 usable mask
+ *     n_ij = sum_s m_i m_j,  A_ij = sum_s y_i m_j,  Q_ij = sum_s y_i^2 m_j,  P_ij = sum_s y_i y_j,
+ *     cov_ij = P_ij - A_ij A_ji / n_ij,  var_i|j = Q_ij - A_ij^2 / n_ij,
+ *     corr_ij = cov_ij / (sqrt(var_i|j) sqrt(var_j|i)).
+ *   The four sums are f64 matrix-core products over the stock axis (v_mfma_f64_16x16x4_f64).
+ * moments: per (row, day) n and sum of x over the usable set of the local S stocks
+ *   -> [rows][D][2] (stock shards: all-gather, centre = sum of sums / sum of n).
+ * sums: the four rows x rows planes of the local stocks -> sums [D][4][rows][rows] (n, A, Q,
+ *   P; plane entry [i][j]); center [rows][D], or NULL: each row's own mean over the local
+ *   usable set, computed by the call in `workspace` (mff_xs_corr_workspace_bytes bytes; may
+ *   be NULL when center is given).
+ * finalize: add the R shards' planes in rank order and apply the definition -> corr f64, n
+ *   int32, both [D][rows][rows].
+ * mean: per (i, j) the mean over days of the non-NaN corr entries, summed in day order
+ *   -> mean f64 (NaN when there is none), days int32 (their count), both [rows][rows].
+ * Errors (negative, nothing launched): rows < 1, rows > max_rows(), min_pairs < 2, a negative
+ * size.  D == 0 or S == 0 is a success (empty result; all-zero planes, NaN corr, n = 0).
+ */
+int mff_xs_corr_max_rows(void); /* 1024 */
+size_t mff_xs_corr_workspace_bytes(int rows, int D, int S);
+int mff_xs_corr_moments(const double* val, const uint8_t* state, int rows, int D, int S,
+                        double* moments, void* stream);
+int mff_xs_corr_sums(const double* val, const uint8_t* state, int rows, int D, int S,
+                     const double* center, double* sums, void* workspace, void* stream);
+int mff_xs_corr_finalize(const double* sums_all /* [R][D][4][rows][rows] */, int R, int rows, int D,
+                         int min_pairs, double* corr, int32_t* n, void* stream);
+int mff_xs_corr_mean(const double* corr, int rows, int D, double* mean, int32_t* days, void* stream);
+
+/*
  * Factor IC / rank-IC test.  Replaces Factor.ic_test
  * (Factor.py:127-229).  Inputs are dense [D][S] (val, state) like stage 1's output rows.
  * mff_future_return: Factor.py:142-162 — per stock over its present days,

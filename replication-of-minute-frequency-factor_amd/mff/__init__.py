@@ -11,3 +11,13 @@ over libmff.so (hand-written HIP for gfx950):
 from . import catalog  # noqa: F401
 
 __version__ = "0.1.0"
+
+__all__ = ["catalog", "factor_correlation"]
+
+
+def __getattr__(name):
+    # mff.factor_correlation, resolved on first use (mff.factor pulls in pandas-side helpers)
+    if name == "factor_correlation":
+        from .factor import factor_correlation
+        return factor_correlation
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

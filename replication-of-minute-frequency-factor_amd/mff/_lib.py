@@ -54,6 +54,12 @@ SIGNATURES = {
     "mff_xs_neutralize_max_groups": (c_int, []),
     "mff_xs_neutralize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mff_xs_neutralize": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, P, ctypes.c_double, c_int, P, P, P, P]),
+    "mff_xs_corr_max_rows": (c_int, []),
+    "mff_xs_corr_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mff_xs_corr_moments": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "mff_xs_corr_sums": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
+    "mff_xs_corr_finalize": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    "mff_xs_corr_mean": (c_int, [P, c_int, c_int, P, P, P]),
     "mff_future_return": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "mff_ic_pairs": (c_int, [P, P, P, P, c_int, c_int, P, P, P]),
     "mff_ic_moments": (c_int, [P, P, c_int, c_int, P, P]),

@@ -993,6 +993,96 @@ def neutralize(val: torch.Tensor, state: torch.Tensor, group: Optional[torch.Ten
     return ov[:rows].contiguous(), os_[:rows].contiguous()
 
 
+CORR_METHODS = ("pearson", "spearman")
+CORR_GATHER_BYTES = 256 << 20  # cap of the gathered sum planes of one day batch (sharded)
+CORR_PLANE_BYTES = 4 << 30     # cap of the sum planes of one day batch (single rank)
+
+
+def factor_corr(val: torch.Tensor, state: torch.Tensor, method: str = "pearson", min_pairs: int = 2,
+                comm=None, stocks_total: Optional[int] = None):
+    """Per-day pairwise correlation of the exposure rows [F][D][S_loc] (mff_xs_corr_*; the
+    definition is on the declarations in include/mff.h): pairwise-complete Pearson over the
+    stocks where both rows hold a finite VALUE, NaN below ``min_pairs`` common stocks or when
+    a side is constant on them.
+
+    ``method='spearman'``: every row is first replaced, per day, by its average ranks over
+    its OWN usable set (``cross_section(kind='rank')`` after non-finite values are masked to
+    NULL), then the Pearson definition is applied to the ranks.  The ranks are NOT recomputed
+    inside each pair set: this equals ``pandas.DataFrame.corr(method='spearman')`` when the
+    rows share their coverage, and is the usual choice for factor panels.
+
+    Stock-sharded (``comm``): the local (n, sum) of every row and day are all-gathered and
+    combined into one common centre, the local sum planes are all-gathered in day batches
+    (at most 256 MiB gathered at a time) and added in rank order; every rank returns the full
+    result.  Returns (corr float64 [D][F][F], n int32 [D][F][F])."""
+    lib = _lib.load()
+    if method not in CORR_METHODS:
+        raise ValueError(f"method must be one of {CORR_METHODS}, got {method!r}")
+    if isinstance(min_pairs, bool) or not isinstance(min_pairs, (int, np.integer)) or min_pairs < 2:
+        raise ValueError(f"min_pairs must be an integer >= 2, got {min_pairs!r}")
+    if val.dim() != 3 or state.shape != val.shape:
+        raise ValueError("val and state must be [rows][D][S]")
+    rows, D, S = val.shape
+    if rows < 1 or rows > lib.mff_xs_corr_max_rows():
+        raise _lib.MffError(f"factor_corr: rows={rows} outside [1, {lib.mff_xs_corr_max_rows()}]")
+    dev = val.device
+    st = _stream(dev)
+    val, state = val.to(torch.float64).contiguous(), state.to(torch.uint8).contiguous()
+    if method == "spearman":
+        masked = torch.where((state == VALUE) & ~torch.isfinite(val), torch.full_like(state, NULL), state)
+        val, state = cross_section(val, masked, "rank", comm=comm, stocks_total=stocks_total)
+    min_pairs = int(min_pairs)
+    corr = torch.empty((D, rows, rows), dtype=torch.float64, device=dev)
+    n = torch.empty((D, rows, rows), dtype=torch.int32, device=dev)
+    if D == 0:
+        return corr, n
+    R = 1 if comm is None else comm.world_size
+    center = None
+    if comm is not None:
+        mom = torch.empty((rows, D, 2), dtype=torch.float64, device=dev)
+        _lib.check(lib.mff_xs_corr_moments(_lib.ptr(val), _lib.ptr(state), rows, D, S, _lib.ptr(mom), st),
+                   "mff_xs_corr_moments")
+        parts = comm.all_gather(mom)
+        tot = parts[0]  # [rows][D][2], the ranks added in rank order: the same bits on every rank
+        for r in range(1, R):
+            tot = tot + parts[r]
+        center = torch.where(tot[..., 0] > 0, tot[..., 1] / tot[..., 0].clamp(min=1.0),
+                             torch.zeros((), dtype=torch.float64, device=dev)).contiguous()
+    ws = torch.empty(max(lib.mff_xs_corr_workspace_bytes(rows, D, S), 8), dtype=torch.uint8, device=dev)
+    day_bytes = 4 * rows * rows * 8
+    nd_max = max(1, (CORR_PLANE_BYTES if comm is None else CORR_GATHER_BYTES // R) // day_bytes)
+    for d0 in range(0, D, nd_max):
+        nd = min(nd_max, D - d0)
+        whole = nd == D
+        v = val if whole else val[:, d0:d0 + nd].contiguous()
+        s_ = state if whole else state[:, d0:d0 + nd].contiguous()
+        c = None if center is None else (center if whole else center[:, d0:d0 + nd].contiguous())
+        sums = torch.empty((nd, 4, rows, rows), dtype=torch.float64, device=dev)
+        _lib.check(lib.mff_xs_corr_sums(_lib.ptr(v), _lib.ptr(s_), rows, nd, S, _lib.ptr(c), _lib.ptr(sums),
+                                        _lib.ptr(ws), st), "mff_xs_corr_sums")
+        sums_all = sums if comm is None else comm.all_gather(sums).contiguous()
+        _lib.check(lib.mff_xs_corr_finalize(_lib.ptr(sums_all), R, rows, nd, min_pairs, _lib.ptr(corr[d0:]),
+                                            _lib.ptr(n[d0:]), st), "mff_xs_corr_finalize")
+    return corr, n
+
+
+def factor_corr_mean(corr: torch.Tensor):
+    """Time aggregate of :func:`factor_corr`'s corr [D][F][F]: per pair the mean over the
+    days where it is not NaN (summed in day order; NaN when there is none) and that count.
+    Returns (mean float64 [F][F], days int32 [F][F])."""
+    lib = _lib.load()
+    if corr.dim() != 3 or corr.shape[1] != corr.shape[2]:
+        raise ValueError("corr must be [D][F][F]")
+    D, rows, _ = corr.shape
+    corr = corr.to(torch.float64).contiguous()
+    dev = corr.device
+    mean = torch.empty((rows, rows), dtype=torch.float64, device=dev)
+    days = torch.empty((rows, rows), dtype=torch.int32, device=dev)
+    _lib.check(lib.mff_xs_corr_mean(_lib.ptr(corr), rows, D, _lib.ptr(mean), _lib.ptr(days), _stream(dev)),
+               "mff_xs_corr_mean")
+    return mean, days
+
+
 def future_return(pct_val: torch.Tensor, pct_state: torch.Tensor, N: int):
     """Factor.py:142-162 on dense [D][S] daily pct_change rows: compounded return of the
     next N present days per stock (mff_future_return).  Returns (val, state) [D][S]."""

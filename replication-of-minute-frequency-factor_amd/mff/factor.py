@@ -303,6 +303,95 @@ class Factor:
         name = f"{self.factor_name}_neu"
         return type(self)(name, frames.to_long(ov[0].cpu().numpy(), os_[0].cpu().numpy(), codes, dates, name))
 
+    def corr_with(self, others, **kw):
+        """The row of this factor in :func:`factor_correlation` of ``[self, *others]``
+        (``others``: a Factor, a sequence of them or a mapping name -> Factor; keywords
+        as there): a pandas Series indexed by the others' names -- with
+        ``return_daily=True`` also the daily long frame restricted to this factor's pairs."""
+        if isinstance(others, Factor):
+            others = [others]
+        if isinstance(others, dict):
+            if self.factor_name in others:
+                raise ValueError(f"duplicate factor name {self.factor_name!r}")
+            group = {self.factor_name: self, **others}
+        else:
+            group = [self] + list(others)
+        out = factor_correlation(group, **kw)
+        mean, daily = out if isinstance(out, tuple) else (out, None)
+        row = mean.loc[self.factor_name].drop(self.factor_name)
+        if daily is None:
+            return row
+        mine = (daily["factor_a"] == self.factor_name) | (daily["factor_b"] == self.factor_name)
+        return row, daily[mine].reset_index(drop=True)
+
+
+def factor_correlation(factors, method: str = "pearson", min_pairs: int = 2, return_daily: bool = False,
+                       device=None):
+    """Cross-sectional correlation matrix of several factors' exposures on the GPU
+    (mff_xs_corr_*, include/mff.h): per date the pairwise-complete Pearson correlation of
+    every pair over the codes where both hold a finite value, then the mean over the dates
+    where it is defined.  No reference counterpart: Factor.py never relates two factors.
+
+    ``factors``: a sequence of :class:`Factor` objects or a mapping name -> Factor (the
+    mapping's keys name the rows); duplicate names raise ValueError.  The exposures are
+    aligned on the union of their codes and dates; a stock-day missing from a factor's frame
+    is absent for that factor.  ``method``: 'pearson' or 'spearman' (each factor ranked per
+    date over its own finite values; the ranks are not recomputed per pair, which equals
+    ``pandas.corr(method='spearman')`` when the factors share their coverage).
+    ``min_pairs`` >= 2: fewer common codes on a date give NaN for that date.
+
+    Returns the F x F pandas DataFrame of the time means (index and columns = the names);
+    with ``return_daily=True`` also a long frame [date, factor_a, factor_b, corr, n] of the
+    upper triangle (in the order of ``factors``) including the diagonal, rows with n >= 1
+    only, sorted by (date, factor_a, factor_b)."""
+    import torch
+
+    from . import engine
+    from .factors import _device
+
+    pd = _pd()
+    if method not in engine.CORR_METHODS:
+        raise ValueError(f"method must be one of {engine.CORR_METHODS}, got {method!r}")
+    if isinstance(min_pairs, bool) or not isinstance(min_pairs, (int, np.integer)) or min_pairs < 2:
+        raise ValueError(f"min_pairs must be an integer >= 2, got {min_pairs!r}")
+    if isinstance(factors, dict):
+        names, objs = [str(k) for k in factors.keys()], list(factors.values())
+    else:
+        objs = list(factors)
+        names = [f.factor_name for f in objs]
+    if not objs:
+        raise ValueError("factor_correlation needs at least one factor")
+    seen = set()
+    for nm in names:
+        if nm in seen:
+            raise ValueError(f"duplicate factor name {nm!r}")
+        seen.add(nm)
+    exposures = [f.factor_exposure for f in objs]
+    codes, dates = frames.universe(*exposures)
+    F, D, S = len(objs), len(dates), len(codes)
+    val = np.zeros((F, D, S), dtype=np.float64)
+    state = np.zeros((F, D, S), dtype=np.uint8)
+    for i, (f, ex) in enumerate(zip(objs, exposures)):
+        val[i], state[i], _, _ = frames.from_long(ex, f.factor_name, codes=codes, dates=dates)
+    dev = _device(device)
+    corr, n = engine.factor_corr(torch.from_numpy(val).to(dev), torch.from_numpy(state).to(dev), method=method,
+                                 min_pairs=int(min_pairs))
+    mean, _ = engine.factor_corr_mean(corr)
+    torch.cuda.synchronize(dev)
+    out = pd.DataFrame(mean.cpu().numpy(), index=list(names), columns=list(names))
+    if not return_daily:
+        return out
+    corr, n = corr.cpu().numpy(), n.cpu().numpy()
+    iu, ju = np.triu_indices(F)
+    keep = n[:, iu, ju] >= 1                      # [D][pairs]
+    d_idx, p_idx = np.nonzero(keep)
+    nm = np.asarray(names, dtype=object)
+    daily = pd.DataFrame({"date": np.asarray(dates, dtype=object)[d_idx],
+                          "factor_a": nm[iu[p_idx]], "factor_b": nm[ju[p_idx]],
+                          "corr": corr[d_idx, iu[p_idx], ju[p_idx]],
+                          "n": n[d_idx, iu[p_idx], ju[p_idx]]})
+    return out, daily.sort_values(["date", "factor_a", "factor_b"], kind="stable").reset_index(drop=True)
+
 
 def rebalance_periods(dates, frequency: str):
     """group_by_dynamic(every=1w/1mo/1q/1y, label='right') windows (Factor.py:249-256,
