@@ -413,6 +413,86 @@ int mff_xs_corr_finalize(const double* sums_all /* [R][D][4][rows][rows] */, int
 int mff_xs_corr_mean(const double* corr, int rows, int D, double* mean, int32_t* days, void* stream);
 
 /*
+ * Per-day multi-factor cross-sectional regression (Fama-MacBeth / pure factor returns):
+ * per day the weighted least squares of a regressand on industry dummies and K exposure
+ * rows, with t-statistics and R^2, and the time aggregate of the coefficients.  No reference
+ * function (Factor.py never regresses); this is the build's definition,
+ * restated in numpy by tests/xs_reg_ref.py.
+ *   Inputs: x [K][D][S] (val f64, state u8), y [D][S] (val, state), optional weight /
+ *   weight_state [D][S] (the WLS weight itself; NULL = all 1), optional group int32 [D][S]
+ *   with ids in [0, G), anything else = none (NULL = no industries: one group, i.e. a plain
+ *   intercept), min_obs.
+ *   Usable set U of a day (listwise): every one of the K rows VALUE and finite, y VALUE and
+ *     finite, the weight VALUE, finite and > 0 when weights are given, an industry when group
+ *     is given.  n = |U| (int32) is always written and exact.
+ *   Model: WLS of y on [dummies of the non-empty industries | x_1..x_K] by Frisch-Waugh: with
+ *     the weighted means over U and g, x~ = x - mean_g(x), y~ = y - mean_g(y),
+ *     M = sum_U w x~ x~^T (K x K), b = sum_U w x~ y~, T = sum_U w y~^2, beta solves M beta = b.
+ *     M, b and T are accumulated on the centred values (f64 matrix-core products over the
+ *     stock axis, v_mfma_f64_16x16x4_f64); raw second moments are never differenced.
+ *   dof = n - K - G_ne, G_ne = the non-empty industries among U (1 without group).
+ *     n < max(min_obs, 1) or dof < 1: status 1, beta, t and r2 of the day NaN.
+ *   Singular rule (counting and fixed thresholds only): column j is constant within
+ *     industries when M_jj <= 1e-20 * sum_U w x_j^2 (the raw second moment); otherwise M is
+ *     scaled to a unit diagonal and factored by an unpivoted f64 Cholesky, a pivot <= 1e-10
+ *     = collinear.  Either case: status 2, NaN outputs for the day.
+ *   Constant regressand, by the same threshold: T <= 1e-20 * sum_U w y^2 is an exact fit,
+ *     b and T count as 0 (beta = 0, RSS = 0, t NaN).
+ *   Outputs per day: beta [D][K]; RSS = max(T - b^T beta, 0), sigma^2 = RSS / dof,
+ *     se_j = sqrt(sigma^2 (M^-1)_jj), tstat [D][K] = beta_j / se_j (NaN when se_j == 0);
+ *     r2 [D] = 1 - RSS / (T + sum_g W_g (ybar_g - ybar_w)^2), the denominator being
+ *     sum_U w (y - ybar_w)^2 of the intercept-only model, NaN when it is <= 1e-20 * sum_U w y^2;
+ *     n, dof, status int32 [D].
+ *   Residual: e = y~ - x~^T beta [D][S]; state VALUE on U, NULL where y is VALUE but the
+ *     stock is outside U and everywhere on a day with status != 0; ABSENT / NULL of y kept.
+ *   Time aggregate per factor over the status-0 days, added in day order: agg [K][6] =
+ *     (days, mean beta, std ddof = 1 (NaN when days < 2), t_fm = mean / (std / sqrt(days)), NaN
+ *     when days < 2 or std == 0, mean |t|, share of |t| > 2 -- the last two over the status-0
+ *     days whose t is not NaN, NaN when there is none); overall [2] = (mean r2 over the
+ *     status-0 days with an r2, mean n over the status-0 days).
+ *   The result is bit-identical from run to run (fixed summation orders: stock order inside
+ *   an MFMA chain, wave order, plane order, day order; no floating-point atomics).
+ * workspace: mff_xs_reg_workspace_bytes(K, D, S, G) bytes of device scratch shared by the
+ *   calls of one regression (G = 0 without group): per-day scalars f64 [D][K + 5], the means
+ *   table f64 [D][max(G, 1)][K + 1], the usable-set plane int32 [D][S] (the stock's industry,
+ *   0 without group, inside U; -1 outside), each part 256-B aligned, in that order.
+ * groups: the usable-set plane (into workspace) and the local group sums
+ *   gsums f64 [nsplit][D][Ge + 1][K + 3], Ge = max(G, 1), one plane per run of the stocks (cut
+ *   into nsplit runs of whole 32-stock tiles): row g < Ge = (n_g, W_g, sum w c for the K + 1
+ *   columns: the x rows, then y), row Ge = (0, 0, the raw sum w c^2 of each column).
+ * gram: adds the R planes of group sums [R][D][Ge + 1][K + 3] (shards x runs) in plane order
+ *   into the means table and the per-day scalars (workspace), then the local Gram planes
+ *   sum w c~ c~^T of the K + 1 columns -> gram f64 [nsplit][D][K + 1][K + 1], one workgroup per
+ *   (day, run of the stocks).
+ * solve: adds the P planes [P][D][K + 1][K + 1] (shards x splits) in plane order and applies
+ *   the definition.  Needs the workspace gram filled.
+ * residual: the residual of the local stocks from beta, status and the workspace.
+ * mean: the time aggregate.
+ * Errors (negative, nothing launched, nothing written): K < 1, K > max_factors(), G outside
+ * [1, max_groups()] with group given (gram / residual: outside [0, max_groups()]), a negative
+ * size, a weight without its state, min_obs < 0.  D == 0 or S == 0 is a success (empty
+ * result; n = 0, status 1, NaN outputs).
+ */
+int mff_xs_reg_max_factors(void); /* 63: K + 1 columns fill one 64-row block */
+int mff_xs_reg_max_groups(void);  /* 256 */
+size_t mff_xs_reg_workspace_bytes(int K, int D, int S, int G);
+int mff_xs_reg_groups(const double* x_val, const uint8_t* x_state, int K, int D, int S,
+                      const double* y_val, const uint8_t* y_state, const double* weight,
+                      const uint8_t* weight_state, const int32_t* group, int G, int nsplit,
+                      double* gsums, void* workspace, void* stream);
+int mff_xs_reg_gram(const double* x_val, int K, int D, int S, const double* y_val,
+                    const double* weight, int G /* 0 = no industries */, const double* gsums_all, int R,
+                    int nsplit, double* gram, void* workspace, void* stream);
+int mff_xs_reg_solve(const double* gram_all, int P, int K, int D, int min_obs, double* beta,
+                     double* tstat, double* r2, int32_t* n, int32_t* dof, int32_t* status,
+                     void* workspace, void* stream);
+int mff_xs_reg_residual(const double* x_val, int K, int D, int S, const double* y_val,
+                        const uint8_t* y_state, int G, const double* beta, const int32_t* status,
+                        double* out_val, uint8_t* out_state, void* workspace, void* stream);
+int mff_xs_reg_mean(const double* beta, const double* tstat, const double* r2, const int32_t* n,
+                    const int32_t* status, int K, int D, double* agg, double* overall, void* stream);
+
+/*
  * Factor IC / rank-IC test.  Replaces Factor.ic_test
  * (Factor.py:127-229).  Inputs are dense [D][S] (val, state) like stage 1's output rows.
  * mff_future_return: Factor.py:142-162 — per stock over its present days,

@@ -12,12 +12,15 @@ from . import catalog  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["catalog", "factor_correlation"]
+__all__ = ["catalog", "factor_correlation", "factor_returns"]
 
 
 def __getattr__(name):
-    # mff.factor_correlation, resolved on first use (mff.factor pulls in pandas-side helpers)
+    # mff.factor_correlation / mff.factor_returns, resolved on first use (mff.factor pulls in pandas-side helpers)
     if name == "factor_correlation":
         from .factor import factor_correlation
         return factor_correlation
+    if name == "factor_returns":
+        from .factor import factor_returns
+        return factor_returns
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -17,7 +17,7 @@ from __future__ import annotations
 import os
 import threading
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -1081,6 +1081,143 @@ def factor_corr_mean(corr: torch.Tensor):
     _lib.check(lib.mff_xs_corr_mean(_lib.ptr(corr), rows, D, _lib.ptr(mean), _lib.ptr(days), _stream(dev)),
                "mff_xs_corr_mean")
     return mean, days
+
+
+REG_SPLIT_DAYS = 256   # below one day per CU (256 on MI355X) the stocks of a day are split
+REG_SPLIT_STOCKS = 256  # ... into runs of at least 8 tiles of 32 stocks
+REG_AGG_COLUMNS = ("days", "mean", "std", "t_fm", "mean_abs_t", "share_abs_t_gt_2")
+
+
+class RegressResult(NamedTuple):
+    """factor_regress: per-day device tensors (resid_* None unless asked for)."""
+    beta: torch.Tensor     # float64 [D][K]
+    tstat: torch.Tensor    # float64 [D][K]
+    r2: torch.Tensor       # float64 [D]
+    n: torch.Tensor        # int32 [D]
+    dof: torch.Tensor      # int32 [D]
+    status: torch.Tensor   # int32 [D]: 0 ok, 1 too few observations, 2 singular
+    resid_val: Optional[torch.Tensor] = None    # float64 [D][S_loc]
+    resid_state: Optional[torch.Tensor] = None  # uint8 [D][S_loc]
+
+
+def reg_splits(D: int, S: int) -> int:
+    """Stock runs per day of the group and Gram passes: 1 from REG_SPLIT_DAYS days on (every CU has a
+    day of its own), below that enough runs for about two workgroups per CU, none shorter
+    than REG_SPLIT_STOCKS stocks."""
+    if D >= REG_SPLIT_DAYS or D < 1:
+        return 1
+    return max(1, min(-(-S // REG_SPLIT_STOCKS), -(-2 * REG_SPLIT_DAYS // D)))
+
+
+def factor_regress(x_val: torch.Tensor, x_state: torch.Tensor, y_val: torch.Tensor, y_state: torch.Tensor,
+                   weight: Optional[torch.Tensor] = None, weight_state: Optional[torch.Tensor] = None,
+                   group: Optional[torch.Tensor] = None, G: Optional[int] = None, min_obs: int = 0,
+                   residual: bool = False, comm=None, stocks_total: Optional[int] = None,
+                   split: Optional[int] = None) -> RegressResult:
+    """Per-day weighted least squares of y [D][S_loc] on industry dummies and the K exposure
+    rows x [K][D][S_loc] (mff_xs_reg_*; the definition is on the declarations in
+    include/mff.h): coefficients, t-statistics, R^2, n, dof and status per day, and with
+    ``residual=True`` the residual of the local stocks.
+
+    ``weight`` / ``weight_state``: the WLS weight itself (None: 1); ``group``: int32 industry
+    ids in [0, G), anything else = none (None: a plain intercept); ``G``: the number of
+    industries (None: the largest id + 1, agreed over the ranks); ``min_obs``: fewer usable
+    stocks give status 1.  ``split``: stock runs per day of the group and Gram passes
+    (None: :func:`reg_splits`; sharded: 1); the runs are added like shards, in run order.
+
+    Stock-sharded (``comm``): the local group sums are all-gathered and added in rank order
+    into one common means table (a shard may hold no member of an industry), the local Gram
+    planes are all-gathered in day batches (at most 256 MiB gathered at a time) and added in
+    rank order; the residual is local; every rank returns the full per-day result."""
+    lib = _lib.load()
+    if x_val.dim() != 3 or x_state.shape != x_val.shape:
+        raise ValueError("x_val and x_state must be [K][D][S]")
+    K, D, S = x_val.shape
+    if K < 1 or K > lib.mff_xs_reg_max_factors():
+        raise _lib.MffError(f"factor_regress: K={K} outside [1, {lib.mff_xs_reg_max_factors()}]")
+    if isinstance(min_obs, bool) or not isinstance(min_obs, (int, np.integer)) or min_obs < 0:
+        raise ValueError(f"min_obs must be an integer >= 0, got {min_obs!r}")
+    if (weight is None) != (weight_state is None):
+        raise ValueError("weight and weight_state go together")
+    for name, t in (("y_val", y_val), ("y_state", y_state), ("weight", weight), ("weight_state", weight_state),
+                    ("group", group)):
+        if t is not None and tuple(t.shape) != (D, S):
+            raise ValueError(f"{name} must be [D][S] = [{D}][{S}], got {tuple(t.shape)}")
+    dev = x_val.device
+    st = _stream(dev)
+    f64, u8 = torch.float64, torch.uint8
+    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
+    y_val, y_state = y_val.to(f64).contiguous(), y_state.to(u8).contiguous()
+    if weight is not None:
+        weight, weight_state = weight.to(f64).contiguous(), weight_state.to(u8).contiguous()
+    Gk = 0
+    if group is not None:
+        group = group.to(torch.int32).contiguous()
+        if G is None:
+            G = int(group.max().item()) + 1 if group.numel() else 1
+            if comm is not None:
+                G = _agreed_max(comm, G, dev)
+            G = max(G, 1)
+        if G < 1 or G > lib.mff_xs_reg_max_groups():
+            raise _lib.MffError(f"factor_regress: {G} industries outside [1, {lib.mff_xs_reg_max_groups()}]")
+        Gk = int(G)
+    Ge = max(Gk, 1)
+    R = 1 if comm is None else comm.world_size
+    beta = torch.empty((D, K), dtype=f64, device=dev)
+    tstat = torch.empty((D, K), dtype=f64, device=dev)
+    r2 = torch.empty(D, dtype=f64, device=dev)
+    n = torch.empty(D, dtype=torch.int32, device=dev)
+    dof = torch.empty(D, dtype=torch.int32, device=dev)
+    status = torch.empty(D, dtype=torch.int32, device=dev)
+    rv = torch.empty((D, S), dtype=f64, device=dev) if residual else None
+    rs = torch.empty((D, S), dtype=u8, device=dev) if residual else None
+    C = K + 1
+    nsplit = int(split) if split is not None else (reg_splits(D, S) if comm is None else 1)
+    if nsplit < 1:
+        raise ValueError(f"split must be >= 1, got {split!r}")
+    day_bytes = nsplit * C * C * 8
+    nd_max = max(1, (CORR_PLANE_BYTES if comm is None else CORR_GATHER_BYTES // R) // day_bytes)
+    for d0 in range(0, D, nd_max):
+        nd = min(nd_max, D - d0)
+        whole = nd == D
+        cut = lambda t_: t_ if (t_ is None or whole) else t_[d0:d0 + nd].contiguous()
+        xv = x_val if whole else x_val[:, d0:d0 + nd].contiguous()
+        xs = x_state if whole else x_state[:, d0:d0 + nd].contiguous()
+        yv, ys, wv, ws_, gp = cut(y_val), cut(y_state), cut(weight), cut(weight_state), cut(group)
+        ws = torch.empty(max(lib.mff_xs_reg_workspace_bytes(K, nd, S, Gk), 8), dtype=u8, device=dev)
+        gsums = torch.empty((nsplit, nd, Ge + 1, K + 3), dtype=f64, device=dev)
+        _lib.check(lib.mff_xs_reg_groups(_lib.ptr(xv), _lib.ptr(xs), K, nd, S, _lib.ptr(yv), _lib.ptr(ys),
+                                         _lib.ptr(wv), _lib.ptr(ws_), _lib.ptr(gp), Gk, nsplit, _lib.ptr(gsums),
+                                         _lib.ptr(ws), st), "mff_xs_reg_groups")
+        gs_all = gsums if comm is None else comm.all_gather(gsums).contiguous()
+        gram = torch.empty((nsplit, nd, C, C), dtype=f64, device=dev)
+        _lib.check(lib.mff_xs_reg_gram(_lib.ptr(xv), K, nd, S, _lib.ptr(yv), _lib.ptr(wv), Gk, _lib.ptr(gs_all),
+                                       R * nsplit, nsplit, _lib.ptr(gram), _lib.ptr(ws), st), "mff_xs_reg_gram")
+        gram_all = gram if comm is None else comm.all_gather(gram).contiguous()
+        _lib.check(lib.mff_xs_reg_solve(_lib.ptr(gram_all), R * nsplit, K, nd, int(min_obs), _lib.ptr(beta[d0:]),
+                                        _lib.ptr(tstat[d0:]), _lib.ptr(r2[d0:]), _lib.ptr(n[d0:]),
+                                        _lib.ptr(dof[d0:]), _lib.ptr(status[d0:]), _lib.ptr(ws), st),
+                   "mff_xs_reg_solve")
+        if residual:
+            _lib.check(lib.mff_xs_reg_residual(_lib.ptr(xv), K, nd, S, _lib.ptr(yv), _lib.ptr(ys), Gk,
+                                               _lib.ptr(beta[d0:]), _lib.ptr(status[d0:]), _lib.ptr(rv[d0:]),
+                                               _lib.ptr(rs[d0:]), _lib.ptr(ws), st), "mff_xs_reg_residual")
+    return RegressResult(beta, tstat, r2, n, dof, status, rv, rs)
+
+
+def factor_regress_mean(res: RegressResult):
+    """Time aggregate (Fama-MacBeth) of :func:`factor_regress` over the status-0 days, in day
+    order.  Returns (agg float64 [K][6] with the columns REG_AGG_COLUMNS, overall float64 [2]
+    = (mean r2, mean n))."""
+    lib = _lib.load()
+    D, K = res.beta.shape
+    dev = res.beta.device
+    agg = torch.empty((K, len(REG_AGG_COLUMNS)), dtype=torch.float64, device=dev)
+    overall = torch.empty(2, dtype=torch.float64, device=dev)
+    _lib.check(lib.mff_xs_reg_mean(_lib.ptr(res.beta), _lib.ptr(res.tstat), _lib.ptr(res.r2), _lib.ptr(res.n),
+                                   _lib.ptr(res.status), K, D, _lib.ptr(agg), _lib.ptr(overall), _stream(dev)),
+               "mff_xs_reg_mean")
+    return agg, overall
 
 
 def future_return(pct_val: torch.Tensor, pct_state: torch.Tensor, N: int):

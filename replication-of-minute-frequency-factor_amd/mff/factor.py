@@ -260,29 +260,7 @@ class Factor:
         ex = self.factor_exposure
         codes, dates = frames.universe(ex)
         D, S = len(dates), len(codes)
-        grp, G = None, None
-        if industry is not None:
-            cols = list(getattr(industry, "columns", []))
-            if "code" not in cols or "industry" not in cols:
-                raise ValueError("industry must be a frame with columns [code, industry] or "
-                                 "[code, date, industry]")
-            ids, labels = pd.factorize(industry["industry"])  # a null label: -1
-            G = max(len(labels), 1)
-            if G > engine.NEUTRALIZE_MAX_GROUPS:
-                raise ValueError(f"industry holds {G} distinct labels, more than the "
-                                 f"{engine.NEUTRALIZE_MAX_GROUPS} the kernel takes")
-            ids = np.asarray(ids, dtype=np.int64)
-            code_pos = pd.Index(codes).get_indexer(industry["code"].astype(str))
-            grp = np.full((D, S), -1, dtype=np.int32)
-            if "date" in cols:
-                day_pos = pd.Index(dates).get_indexer([frames._as_date(d) for d in industry["date"]])
-                ok = (code_pos >= 0) & (day_pos >= 0)
-                grp[day_pos[ok], code_pos[ok]] = ids[ok]
-            else:
-                ok = code_pos >= 0
-                if len(np.unique(code_pos[ok])) != int(ok.sum()):
-                    raise ValueError("industry without a date column must hold one row per code")
-                grp[:, code_pos[ok]] = ids[ok][None, :]
+        grp, G = _industry_ids(industry, codes, dates)
         dev = _device(device)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         zv = zs = None
@@ -323,6 +301,164 @@ class Factor:
             return row
         mine = (daily["factor_a"] == self.factor_name) | (daily["factor_b"] == self.factor_name)
         return row, daily[mine].reset_index(drop=True)
+
+    def return_with(self, others, **kw):
+        """The row of this factor in :func:`factor_returns` of ``[self, *others]`` (``others``:
+        a Factor, a sequence of them or a mapping name -> Factor; keywords as there): a pandas
+        Series of the aggregate columns -- with ``return_daily`` / ``return_residual`` the
+        extras follow, the daily long frame restricted to this factor."""
+        if isinstance(others, Factor):
+            others = [others]
+        if isinstance(others, dict):
+            if self.factor_name in others:
+                raise ValueError(f"duplicate factor name {self.factor_name!r}")
+            group = {self.factor_name: self, **others}
+        else:
+            group = [self] + list(others)
+        out = factor_returns(group, **kw)
+        if not isinstance(out, tuple):
+            return out.loc[self.factor_name]
+        extras = list(out[1:])
+        if kw.get("return_daily"):
+            extras[0] = extras[0][extras[0]["factor"] == self.factor_name].reset_index(drop=True)
+        return (out[0].loc[self.factor_name], *extras)
+
+
+def _industry_ids(industry, codes, dates):
+    """``industry`` (None, or a long frame [code, industry] / [code, date, industry]; labels of
+    any hashable dtype, a null label = no industry) -> (int32 ids [D][S] with -1 = none, the
+    number of labels G), or (None, None).  Shared by Factor.neutralize and factor_returns."""
+    from . import engine
+
+    pd = _pd()
+    if industry is None:
+        return None, None
+    D, S = len(dates), len(codes)
+    cols = list(getattr(industry, "columns", []))
+    if "code" not in cols or "industry" not in cols:
+        raise ValueError("industry must be a frame with columns [code, industry] or "
+                         "[code, date, industry]")
+    ids, labels = pd.factorize(industry["industry"])  # a null label: -1
+    G = max(len(labels), 1)
+    if G > engine.NEUTRALIZE_MAX_GROUPS:
+        raise ValueError(f"industry holds {G} distinct labels, more than the "
+                         f"{engine.NEUTRALIZE_MAX_GROUPS} the kernel takes")
+    ids = np.asarray(ids, dtype=np.int64)
+    code_pos = pd.Index(codes).get_indexer(industry["code"].astype(str))
+    grp = np.full((D, S), -1, dtype=np.int32)
+    if "date" in cols:
+        day_pos = pd.Index(dates).get_indexer([frames._as_date(d) for d in industry["date"]])
+        ok = (code_pos >= 0) & (day_pos >= 0)
+        grp[day_pos[ok], code_pos[ok]] = ids[ok]
+    else:
+        ok = code_pos >= 0
+        if len(np.unique(code_pos[ok])) != int(ok.sum()):
+            raise ValueError("industry without a date column must hold one row per code")
+        grp[:, code_pos[ok]] = ids[ok][None, :]
+    return grp, G
+
+
+def _named_factors(factors, what):
+    """A sequence of Factor objects or a mapping name -> Factor -> (names, objects);
+    duplicate names raise ValueError."""
+    if isinstance(factors, dict):
+        names, objs = [str(k) for k in factors.keys()], list(factors.values())
+    else:
+        objs = list(factors)
+        names = [f.factor_name for f in objs]
+    if not objs:
+        raise ValueError(f"{what} needs at least one factor")
+    seen = set()
+    for nm in names:
+        if nm in seen:
+            raise ValueError(f"duplicate factor name {nm!r}")
+        seen.add(nm)
+    return names, objs
+
+
+def factor_returns(factors, future_days: int = 1, industry=None, weight: Literal["cmc", "tmc", None] = None,
+                   min_obs: Optional[int] = None, return_daily: bool = False, return_residual: bool = False,
+                   pv_data=None, device=None):
+    """Per-date cross-sectional regression of the forward return on several factors at once
+    (Fama-MacBeth / pure factor returns) on the GPU (mff_xs_reg_*, include/mff.h): weighted
+    least squares of the ``future_days`` compounded return on industry dummies and every
+    factor's exposure over the codes where all of them hold a finite value, then the time
+    aggregate of the coefficients.  No reference counterpart: Factor.py never regresses.
+
+    ``factors``: a sequence of :class:`Factor` or a mapping name -> Factor (duplicate names
+    raise ValueError); the universe is the union of their codes and dates and ``pv_data``
+    (default: the daily price-volume file; columns code, date, pct_change and the weight
+    column).  ``industry``: as in :meth:`Factor.neutralize` (None: a plain intercept).
+    ``weight``: None, or 'cmc' / 'tmc' for w = sqrt(cap); a null, non-finite or <= 0 cap
+    means no weight (the stock-day drops out).  ``min_obs``: fewer usable codes on a date
+    give no result for it (None: 0, only the degrees-of-freedom rule applies).
+
+    Returns a DataFrame indexed by factor name with the columns days, mean, std, t_fm,
+    mean_abs_t, share_abs_t_gt_2, mean_r2, mean_n.  With ``return_daily=True`` also a long
+    frame [date, factor, ret, t] of the dates with a result, sorted by (date, factor in the
+    order given), and a per-date frame [date, n, dof, r2, status]; with
+    ``return_residual=True`` also a :class:`Factor` named "specific_return" holding the
+    residual.  The extras follow the aggregate in that order, as a tuple."""
+    import torch
+
+    from . import engine
+    from .factors import _device
+
+    pd = _pd()
+    if weight not in (None, "tmc", "cmc"):
+        raise ValueError(f"weight must be 'tmc', 'cmc' or None, got {weight!r}")
+    if min_obs is None:
+        min_obs = 0
+    if isinstance(min_obs, bool) or not isinstance(min_obs, (int, np.integer)) or min_obs < 0:
+        raise ValueError(f"min_obs must be an integer >= 0, got {min_obs!r}")
+    names, objs = _named_factors(factors, "factor_returns")
+    need = ["code", "date", "pct_change"] + ([weight] if weight else [])
+    pv = pv_data if pv_data is not None else Factor._read_daily_pv_data(need)
+    for c in need:
+        if c not in pv.columns:
+            raise ValueError(f"pv_data has no column {c!r}")
+    exposures = [f.factor_exposure for f in objs]
+    codes, dates = frames.universe(*exposures, pv)
+    K, D, S = len(objs), len(dates), len(codes)
+    grp, G = _industry_ids(industry, codes, dates)
+    val = np.zeros((K, D, S), dtype=np.float64)
+    state = np.zeros((K, D, S), dtype=np.uint8)
+    for i, (f, ex) in enumerate(zip(objs, exposures)):
+        val[i], state[i], _, _ = frames.from_long(ex, f.factor_name, codes=codes, dates=dates)
+    dev = _device(device)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    pc_v, pc_s, _, _ = frames.from_long(pv, "pct_change", codes=codes, dates=dates)
+    yv, ys = engine.future_return(t(pc_v), t(pc_s), future_days)
+    wv = ws = None
+    if weight is not None:
+        c_v, c_s, _, _ = frames.from_long(pv, weight, codes=codes, dates=dates)
+        cap, cst = t(c_v), t(c_s)
+        ok = (cst == engine.VALUE) & torch.isfinite(cap) & (cap > 0)
+        wv = torch.where(ok, torch.sqrt(torch.where(ok, cap, torch.ones_like(cap))), torch.zeros_like(cap))
+        ws = torch.where(ok, cst, torch.where(cst == engine.ABSENT, cst, torch.full_like(cst, engine.NULL)))
+    res = engine.factor_regress(t(val), t(state), yv, ys, wv, ws, None if grp is None else t(grp), G=G,
+                                min_obs=int(min_obs), residual=bool(return_residual))
+    agg, overall = engine.factor_regress_mean(res)
+    torch.cuda.synchronize(dev)
+    out = pd.DataFrame(agg.cpu().numpy(), index=list(names), columns=list(engine.REG_AGG_COLUMNS))
+    out["days"] = out["days"].astype(np.int64)
+    ov = overall.cpu().numpy()
+    out["mean_r2"], out["mean_n"] = ov[0], ov[1]
+    extras = []
+    if return_daily:
+        status = res.status.cpu().numpy()
+        beta, tst = res.beta.cpu().numpy(), res.tstat.cpu().numpy()
+        d_idx = np.nonzero(status == 0)[0]
+        dd = np.asarray(dates, dtype=object)
+        daily = pd.DataFrame({"date": np.repeat(dd[d_idx], K), "factor": np.tile(np.asarray(names, dtype=object), len(d_idx)),
+                              "ret": beta[d_idx].reshape(-1), "t": tst[d_idx].reshape(-1)})
+        per_date = pd.DataFrame({"date": dd, "n": res.n.cpu().numpy(), "dof": res.dof.cpu().numpy(),
+                                 "r2": res.r2.cpu().numpy(), "status": status})
+        extras += [daily, per_date]
+    if return_residual:
+        extras.append(Factor("specific_return", frames.to_long(res.resid_val.cpu().numpy(), res.resid_state.cpu().numpy(),
+                                                               codes, dates, "specific_return")))
+    return (out, *extras) if extras else out
 
 
 def factor_correlation(factors, method: str = "pearson", min_pairs: int = 2, return_daily: bool = False,
