@@ -493,6 +493,77 @@ int mff_xs_reg_mean(const double* beta, const double* tstat, const double* r2, c
                     const int32_t* status, int K, int D, double* agg, double* overall, void* stream);
 
 /*
+ * Per-day factor orthogonalisation: the K exposure rows of a day are standardised over the
+ * listwise usable set and mapped to K mutually uncorrelated unit-variance rows, symmetrically
+ * (Loewdin) or by Gram-Schmidt in row order.  No reference function (Factor.py never combines
+ * factors); this is the build's definition, restated in numpy by
+ * tests/xs_orth_ref.py.
+ *   Inputs: x [K][D][S] (val f64, state u8), 1 <= K <= 64; method 0 = symmetric, 1 =
+ *   Gram-Schmidt in row order; min_obs >= 0.
+ *   Usable set U of a day (listwise): every one of the K rows VALUE and finite.  n = |U|
+ *     (int32) is always written and exact.
+ *   Standardise: c_j = x_j - mean_U(x_j); M = sum_U c c^T (K x K), accumulated on the centred
+ *     values (f64 matrix-core products over the stock axis, v_mfma_f64_16x16x4_f64; raw second
+ *     moments are never differenced); sigma_j = sqrt(M_jj / (n - 1)), z_j = c_j / sigma_j;
+ *     R_ij = M_ij / sqrt(M_ii M_jj) with the diagonal exactly 1.0, bitwise symmetric.
+ *   Status: 1 when n < max(min_obs, K + 1); otherwise 2 (singular) when a column is constant
+ *     on U (M_jj <= 1e-20 * sum_U x_j^2) or the smallest eigenvalue of R is <= 1e-10 (or the
+ *     eigensolver has not converged in 30 sweeps); otherwise 0.  The eigenvalues of R are
+ *     computed for both methods.
+ *   Transform T [D][K][K], f_j = sum_k z_k T[k][j]:
+ *     symmetric: R = V L V^T (cyclic two-sided Jacobi, round-robin pairing, a pair skipped
+ *       when |a_pq| <= 2^-52 sqrt(|a_pp a_qq|), stop after the first sweep without a
+ *       rotation), T = V L^-1/2 V^T, summed in a fixed k order, entries i <= j computed and
+ *       mirrored: bitwise symmetric;
+ *     Gram-Schmidt: R = L L^T by an unpivoted f64 Cholesky, T = L^-T: upper triangular with
+ *       exact zeros below the diagonal; f_1 = z_1, f_K = the standardised OLS residual of x_K
+ *       on an intercept and the rows before it.
+ *     Either way the K output columns have, on U, mean 0, sample variance 1 (ddof = 1) and
+ *     zero mutual sample covariance.
+ *   Diagnostics per day: eig [D][K] = the eigenvalues of R ascending; keep [D][K] = (R T)_jj
+ *     = corr_U(f_j, x_j) (symmetric: sum_k V_jk^2 sqrt(l_k); Gram-Schmidt: L_jj).  On a day
+ *     with status != 0, T, eig and keep are NaN.
+ *   Output [K][D][S] (val, state): ABSENT stays ABSENT, NULL stays NULL, a VALUE inside U is
+ *     VALUE, a VALUE outside U (a finite value whose stock lacks another factor, a NaN / inf)
+ *     becomes NULL, as does every VALUE of a day with status != 0; the value of a non-VALUE
+ *     entry is 0.0.
+ *   The result is bit-identical from run to run (fixed summation orders, a fixed rotation
+ *   order, no floating-point atomics).
+ * workspace: mff_xs_orth_workspace_bytes(K, D, S) bytes of device scratch shared by the calls
+ *   of one orthogonalisation: per-day scalars f64 [D][2K + 1] = (n, the K means, the K raw
+ *   sums of squares), T'[k][j] = T[k][j] / sigma_k f64 [D][K][K], the usable-set plane u8
+ *   [D][S], each part 256-B aligned, in that order.
+ * sums: the usable-set plane (into workspace) and sums f64 [nsplit][D][2K + 1] = (n, sum_U x_j,
+ *   sum_U x_j^2), one plane per run of the stocks (nsplit runs of whole 32-stock tiles).
+ * gram: adds the R planes of sums [R][D][2K + 1] (shards x runs) in plane order into the
+ *   per-day scalars (workspace), then the local centred Gram planes
+ *   gram f64 [nsplit][D][K][K], one workgroup per (day, run).
+ * solve: adds the P planes [P][D][K][K] in plane order and applies the definition; leaves T'
+ *   in the workspace.  Reads the per-day scalars (n, means, raw sums of squares) that
+ *   mff_xs_orth_gram left in the workspace.
+ * The four calls of one orthogonalisation share one workspace (same K, D, S) and run in the
+ *   order sums -> gram -> solve -> apply on one stream: sums writes the usable-set plane, gram
+ *   the per-day scalars, solve T'; each later call reads what the earlier ones wrote.  The
+ *   workspace needs no initialisation.
+ * apply: out[j] = sum_k T'[k][j] c_k for the local stocks, and the output states.
+ * Errors (negative, nothing launched, nothing written): K < 1, K > max_factors(), method not
+ * 0 / 1, a negative size, min_obs < 0, R / P / nsplit < 1.  D == 0 or S == 0 is a success
+ * (empty result; n = 0, status 1, NaN diagnostics).
+ */
+int mff_xs_orth_max_factors(void); /* 64: the full 64-row block is exposures */
+size_t mff_xs_orth_workspace_bytes(int K, int D, int S);
+int mff_xs_orth_sums(const double* x_val, const uint8_t* x_state, int K, int D, int S, int nsplit,
+                     double* sums, void* workspace, void* stream);
+int mff_xs_orth_gram(const double* x_val, int K, int D, int S, const double* sums_all, int R,
+                     int nsplit, double* gram, void* workspace, void* stream);
+int mff_xs_orth_solve(const double* gram_all, int P, int K, int D, int method, int min_obs,
+                      double* transform, double* eig, double* keep, int32_t* n, int32_t* status,
+                      void* workspace, void* stream);
+int mff_xs_orth_apply(const double* x_val, const uint8_t* x_state, int K, int D, int S,
+                      const int32_t* status, double* out_val, uint8_t* out_state, void* workspace,
+                      void* stream);
+
+/*
  * Factor IC / rank-IC test.  Replaces Factor.ic_test
  * (Factor.py:127-229).  Inputs are dense [D][S] (val, state) like stage 1's output rows.
  * mff_future_return: Factor.py:142-162 — per stock over its present days,

@@ -12,15 +12,19 @@ from . import catalog  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["catalog", "factor_correlation", "factor_returns"]
+__all__ = ["catalog", "factor_correlation", "factor_returns", "orthogonalize"]
 
 
 def __getattr__(name):
-    # mff.factor_correlation / mff.factor_returns, resolved on first use (mff.factor pulls in pandas-side helpers)
+    # mff.factor_correlation / mff.factor_returns / mff.orthogonalize, resolved on first use
+    # (mff.factor pulls in pandas-side helpers)
     if name == "factor_correlation":
         from .factor import factor_correlation
         return factor_correlation
     if name == "factor_returns":
         from .factor import factor_returns
         return factor_returns
+    if name == "orthogonalize":
+        from .factor import orthogonalize
+        return orthogonalize
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

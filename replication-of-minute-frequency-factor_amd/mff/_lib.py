@@ -68,6 +68,12 @@ SIGNATURES = {
     "mff_xs_reg_solve": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
     "mff_xs_reg_residual": (c_int, [P, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P]),
     "mff_xs_reg_mean": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P]),
+    "mff_xs_orth_max_factors": (c_int, []),
+    "mff_xs_orth_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mff_xs_orth_sums": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
+    "mff_xs_orth_gram": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
+    "mff_xs_orth_solve": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    "mff_xs_orth_apply": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "mff_future_return": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "mff_ic_pairs": (c_int, [P, P, P, P, c_int, c_int, P, P, P]),
     "mff_ic_moments": (c_int, [P, P, c_int, c_int, P, P]),

@@ -1220,6 +1220,91 @@ def factor_regress_mean(res: RegressResult):
     return agg, overall
 
 
+ORTH_METHODS = ("symmetric", "schmidt")
+
+
+class OrthResult(NamedTuple):
+    """factor_orthogonalize: the orthogonalised rows and the per-day diagnostics (device tensors)."""
+    val: torch.Tensor        # float64 [K][D][S_loc]
+    state: torch.Tensor      # uint8 [K][D][S_loc]
+    transform: torch.Tensor  # float64 [D][K][K]: f_j = sum_k z_k T[k][j]
+    eig: torch.Tensor        # float64 [D][K]: eigenvalues of the day's correlation matrix, ascending
+    keep: torch.Tensor       # float64 [D][K]: corr_U(f_j, x_j)
+    n: torch.Tensor          # int32 [D]
+    status: torch.Tensor     # int32 [D]: 0 ok, 1 too few observations, 2 singular
+
+
+def factor_orthogonalize(x_val: torch.Tensor, x_state: torch.Tensor, method: str = "symmetric", min_obs: int = 0,
+                         comm=None, stocks_total: Optional[int] = None, split: Optional[int] = None) -> OrthResult:
+    """Per-day orthogonalisation of the K exposure rows x [K][D][S_loc] (mff_xs_orth_*; the
+    definition is on the declarations in include/mff.h): over the stocks where all K rows hold
+    a finite value the rows are standardised and mapped to K uncorrelated unit-variance rows,
+    ``method`` 'symmetric' (Loewdin: the closest orthonormal set, no row preferred) or
+    'schmidt' (Gram-Schmidt in row order: row j with the rows before it taken out).
+
+    ``min_obs``: fewer usable stocks (or fewer than K + 1) give status 1.  ``split``: stock
+    runs per day of the sums and Gram passes (None: :func:`reg_splits`; sharded: 1); the runs
+    are added like shards, in run order.
+
+    Stock-sharded (``comm``): the local sums and the local Gram planes are all-gathered (the
+    planes in day batches of at most 256 MiB gathered at a time) and added in rank order; the
+    apply pass is local; every rank returns the full per-day diagnostics.  ``stocks_total`` is
+    accepted for the call shape of :func:`factor_regress` and ignored: nothing here depends on
+    the width of the other shards."""
+    lib = _lib.load()
+    if x_val.dim() != 3 or x_state.shape != x_val.shape:
+        raise ValueError("x_val and x_state must be [K][D][S]")
+    K, D, S = x_val.shape
+    if K < 1 or K > lib.mff_xs_orth_max_factors():
+        raise _lib.MffError(f"factor_orthogonalize: K={K} outside [1, {lib.mff_xs_orth_max_factors()}]")
+    if method not in ORTH_METHODS:
+        raise ValueError(f"method must be one of {ORTH_METHODS}, got {method!r}")
+    if isinstance(min_obs, bool) or not isinstance(min_obs, (int, np.integer)) or min_obs < 0:
+        raise ValueError(f"min_obs must be an integer >= 0, got {min_obs!r}")
+    dev = x_val.device
+    st = _stream(dev)
+    f64, u8 = torch.float64, torch.uint8
+    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
+    R = 1 if comm is None else comm.world_size
+    ov = torch.empty((K, D, S), dtype=f64, device=dev)
+    os_ = torch.empty((K, D, S), dtype=u8, device=dev)
+    tr = torch.empty((D, K, K), dtype=f64, device=dev)
+    eig = torch.empty((D, K), dtype=f64, device=dev)
+    keep = torch.empty((D, K), dtype=f64, device=dev)
+    n = torch.empty(D, dtype=torch.int32, device=dev)
+    status = torch.empty(D, dtype=torch.int32, device=dev)
+    nsplit = int(split) if split is not None else (reg_splits(D, S) if comm is None else 1)
+    if nsplit < 1:
+        raise ValueError(f"split must be >= 1, got {split!r}")
+    m = ORTH_METHODS.index(method)
+    day_bytes = nsplit * K * K * 8
+    nd_max = max(1, (CORR_PLANE_BYTES if comm is None else CORR_GATHER_BYTES // R) // day_bytes)
+    for d0 in range(0, D, nd_max):
+        nd = min(nd_max, D - d0)
+        whole = nd == D
+        xv = x_val if whole else x_val[:, d0:d0 + nd].contiguous()
+        xs = x_state if whole else x_state[:, d0:d0 + nd].contiguous()
+        bv = ov if whole else torch.empty((K, nd, S), dtype=f64, device=dev)
+        bs = os_ if whole else torch.empty((K, nd, S), dtype=u8, device=dev)
+        ws = torch.empty(max(lib.mff_xs_orth_workspace_bytes(K, nd, S), 8), dtype=u8, device=dev)
+        sums = torch.empty((nsplit, nd, 2 * K + 1), dtype=f64, device=dev)
+        _lib.check(lib.mff_xs_orth_sums(_lib.ptr(xv), _lib.ptr(xs), K, nd, S, nsplit, _lib.ptr(sums), _lib.ptr(ws), st),
+                   "mff_xs_orth_sums")
+        sums_all = sums if comm is None else comm.all_gather(sums).contiguous()
+        gram = torch.empty((nsplit, nd, K, K), dtype=f64, device=dev)
+        _lib.check(lib.mff_xs_orth_gram(_lib.ptr(xv), K, nd, S, _lib.ptr(sums_all), R * nsplit, nsplit,
+                                        _lib.ptr(gram), _lib.ptr(ws), st), "mff_xs_orth_gram")
+        gram_all = gram if comm is None else comm.all_gather(gram).contiguous()
+        _lib.check(lib.mff_xs_orth_solve(_lib.ptr(gram_all), R * nsplit, K, nd, m, int(min_obs), _lib.ptr(tr[d0:]),
+                                         _lib.ptr(eig[d0:]), _lib.ptr(keep[d0:]), _lib.ptr(n[d0:]),
+                                         _lib.ptr(status[d0:]), _lib.ptr(ws), st), "mff_xs_orth_solve")
+        _lib.check(lib.mff_xs_orth_apply(_lib.ptr(xv), _lib.ptr(xs), K, nd, S, _lib.ptr(status[d0:]), _lib.ptr(bv),
+                                         _lib.ptr(bs), _lib.ptr(ws), st), "mff_xs_orth_apply")
+        if not whole:
+            ov[:, d0:d0 + nd], os_[:, d0:d0 + nd] = bv, bs
+    return OrthResult(ov, os_, tr, eig, keep, n, status)
+
+
 def future_return(pct_val: torch.Tensor, pct_state: torch.Tensor, N: int):
     """Factor.py:142-162 on dense [D][S] daily pct_change rows: compounded return of the
     next N present days per stock (mff_future_return).  Returns (val, state) [D][S]."""

@@ -323,6 +323,24 @@ class Factor:
             extras[0] = extras[0][extras[0]["factor"] == self.factor_name].reset_index(drop=True)
         return (out[0].loc[self.factor_name], *extras)
 
+    def orthogonal_to(self, others, **kw) -> "Factor":
+        """This factor with the others taken out: the last output of the Gram-Schmidt
+        :func:`orthogonalize` of ``[*others, self]`` (``others``: a Factor, a sequence of them
+        or a mapping name -> Factor; keywords as there, ``method`` excepted), a new object of
+        this class named ``f"{factor_name}_orth"``."""
+        if "method" in kw or "return_info" in kw:
+            raise ValueError("orthogonal_to is Gram-Schmidt and returns the factor alone")
+        if isinstance(others, Factor):
+            others = [others]
+        if isinstance(others, dict):
+            if self.factor_name in others:
+                raise ValueError(f"duplicate factor name {self.factor_name!r}")
+            group = {**others, self.factor_name: self}
+        else:
+            group = list(others) + [self]
+        out = orthogonalize(group, method="schmidt", **kw)
+        return out[self.factor_name]
+
 
 def _industry_ids(industry, codes, dates):
     """``industry`` (None, or a long frame [code, industry] / [code, date, industry]; labels of
@@ -459,6 +477,69 @@ def factor_returns(factors, future_days: int = 1, industry=None, weight: Literal
         extras.append(Factor("specific_return", frames.to_long(res.resid_val.cpu().numpy(), res.resid_state.cpu().numpy(),
                                                                codes, dates, "specific_return")))
     return (out, *extras) if extras else out
+
+
+def orthogonalize(factors, method: str = "symmetric", min_obs: Optional[int] = None, return_info: bool = False,
+                  device=None):
+    """Per-date orthogonalisation of several factors' exposures on the GPU (mff_xs_orth_*,
+    include/mff.h): over the codes of a date where all of them hold a finite value the
+    exposures are standardised and mapped to as many mutually uncorrelated unit-variance
+    columns.  No reference counterpart: Factor.py never combines factors.
+
+    ``factors``: a sequence of :class:`Factor` or a mapping name -> Factor (duplicate names
+    raise ValueError), aligned on the union of their codes and dates.  ``method``:
+    'symmetric' (Loewdin: the orthonormal set closest to the standardised inputs, no factor
+    preferred) or 'schmidt' (Gram-Schmidt in the order given: each factor with the earlier
+    ones taken out).  ``min_obs``: fewer usable codes on a date (or fewer than the number of
+    factors + 1) give no result for it (None: 0).  A stock-day with a value but outside the
+    usable set, or on a date without a result, comes out null.
+
+    Returns ``{name: Factor}`` in input order, each object of its input's class, named
+    ``f"{name}_orth"`` and holding [code, date, <that name>]; the inputs are untouched.  With
+    ``return_info=True`` also a per-date frame [date, n, status, eig_min, eig_max, cond]
+    (eigenvalues of the date's correlation matrix) and a frame indexed by factor name with
+    days, mean_keep, min_keep over the dates with a result (keep = the correlation of the
+    output with its input), as a tuple."""
+    import torch
+
+    from . import engine
+    from .factors import _device
+
+    pd = _pd()
+    if method not in engine.ORTH_METHODS:
+        raise ValueError(f"method must be one of {engine.ORTH_METHODS}, got {method!r}")
+    if min_obs is None:
+        min_obs = 0
+    if isinstance(min_obs, bool) or not isinstance(min_obs, (int, np.integer)) or min_obs < 0:
+        raise ValueError(f"min_obs must be an integer >= 0, got {min_obs!r}")
+    names, objs = _named_factors(factors, "orthogonalize")
+    exposures = [f.factor_exposure for f in objs]
+    codes, dates = frames.universe(*exposures)
+    K, D, S = len(objs), len(dates), len(codes)
+    val = np.zeros((K, D, S), dtype=np.float64)
+    state = np.zeros((K, D, S), dtype=np.uint8)
+    for i, (f, ex) in enumerate(zip(objs, exposures)):
+        val[i], state[i], _, _ = frames.from_long(ex, f.factor_name, codes=codes, dates=dates)
+    dev = _device(device)
+    res = engine.factor_orthogonalize(torch.from_numpy(val).to(dev), torch.from_numpy(state).to(dev), method=method,
+                                      min_obs=int(min_obs))
+    torch.cuda.synchronize(dev)
+    ov, os_ = res.val.cpu().numpy(), res.state.cpu().numpy()
+    out = {}
+    for i, (nm, f) in enumerate(zip(names, objs)):
+        new = f"{nm}_orth"
+        out[nm] = type(f)(new, frames.to_long(ov[i], os_[i], codes, dates, new))
+    if not return_info:
+        return out
+    status, eig, keep = res.status.cpu().numpy(), res.eig.cpu().numpy(), res.keep.cpu().numpy()
+    per_date = pd.DataFrame({"date": np.asarray(dates, dtype=object), "n": res.n.cpu().numpy(), "status": status,
+                             "eig_min": eig[:, 0], "eig_max": eig[:, -1], "cond": eig[:, -1] / eig[:, 0]})
+    ok = keep[status == 0]
+    days = len(ok)
+    per_factor = pd.DataFrame({"days": np.full(K, days, dtype=np.int64),
+                               "mean_keep": ok.mean(axis=0) if days else np.full(K, np.nan),
+                               "min_keep": ok.min(axis=0) if days else np.full(K, np.nan)}, index=list(names))
+    return out, per_date, per_factor
 
 
 def factor_correlation(factors, method: str = "pearson", min_pairs: int = 2, return_daily: bool = False,
