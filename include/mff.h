@@ -107,7 +107,9 @@ int mff_ingest_rows(const int32_t* stock, const int32_t* day, const int64_t* tim
  * u64 counter per day) and the split key u64 in front.
  * workspace: mff_stage1_workspace_bytes(S, D) bytes of device scratch (the list of
  * stock-days the exact general path finishes; zeroed by the call itself).
- * Environment MFF_STAGE1_IMPL=w64 selects the wave-per-stock-day kernel for everything.
+ * Environment MFF_STAGE1_IMPL=w64 selects the wave-per-stock-day kernel for everything;
+ * MFF_STAGE1G_FULL=0 keeps the group kernel on its general (per-bar presence mask) form
+ * for waves whose stock-days hold every bar (a test hook: the results are the same bits).
  */
 size_t mff_stage1_workspace_bytes(int S, int D);
 /* mff_stage1 in two calls with the same arguments: part 1 = the LVL/PDF group (

@@ -76,6 +76,7 @@ struct GArgs {
   uint32_t fam_exact;  // families whose non-fast stock-days go to the exact list
   uint32_t* ord_th;    // ORD volume thresholds [3][D][S] (top-50 min, top-20 min, bottom-50 max)
                        // for the serial returns kernel's products, or null
+  int full;            // waves of all-present stock-days may take the FULL form of the body
   int S, D;
   uint32_t fam;
   int8_t row[NF];
@@ -95,6 +96,10 @@ struct Res {
   __device__ __forceinline__ void val(int f, double x) { put(f, x, MFF_STATE_VALUE); }
   __device__ __forceinline__ void null(int f) { put(f, 0.0, MFF_STATE_NULL); }
 };
+
+// the sets of sorted families only (every instantiated one): their body has an
+// all-present (FULL) form beside the general one
+constexpr uint32_t kSortedFams = F_ORD | F_ORDV | F_LVL | F_PDF;
 
 __device__ __forceinline__ double gmin_d(double x) {
   x = fmin(x, dpp_d<QP_XOR1>(x));
@@ -191,14 +196,12 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
   // per group: the sorted families need 2 x 240 words (level cumulative volumes and
   // close words; the 256-word key / volume images fit inside), the OLS betas 256 doubles
   constexpr int SW = (SET & F_OLS) ? 2 * NB : 2 * NBAR;  // words
+  constexpr bool SORTED = (SET & ~kSortedFams) == 0u;
   __shared__ __attribute__((aligned(16))) uint64_t scratch[16][SW / 2 + 8];
   const int lane = lane_id();
   const int wave = threadIdx.x >> 6;
   const int grp = lane >> 4;
-  const int g = gi();
-  const int gb = gbase();
-  uint64_t* scr = scratch[wave * 4 + grp];
-  double* scr_d = reinterpret_cast<double*>(scr);
+  const int g0 = gi();
   const uint32_t fam = a.fam & SET;
   const int ntile = (a.S + 16 * kGIter - 1) / (16 * kGIter);
   const int d = blockIdx.x / ntile;
@@ -208,15 +211,43 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
   for (int it = 0; it < kGIter; ++it) {
     const int s = s0 + it * 16 + wave * 4 + grp;
     const bool act = s < a.S;
-    const size_t sd = (size_t)d * a.S + (act ? s : 0);
-    const bool ln = act && g < 15;  // lane holds bars
+    const size_t sd0 = (size_t)d * a.S + (act ? s : 0);
+    const bool ln = act && g0 < 15;  // lane holds bars
 
-    uint32_t pb = 0;
-    if (ln) {
-      const uint32_t w = a.mask[sd * 8 + (g >> 1)];
-      pb = (w >> (16 * (g & 1))) & 0xFFFFu;
+    // lanes 0..14 their 16 presence bits; lane 15 (no bars) the row-set word
+    uint32_t mw = 0u;
+    if (act) mw = a.mask[sd0 * 8 + (g0 < 15 ? g0 >> 1 : 7)];
+    const uint32_t pb0 = g0 < 15 ? (mw >> (16 * (g0 & 1))) & 0xFFFFu : 0u;
+    // FULL: every group of the wave is active, holds all 240 bars and is outside the row
+    // set (wave-uniform).  Presence is then a constant of the lane, n = 240, the first /
+    // last present bars 0 / 239; the arithmetic on bars is the general form's.
+    bool wfull = false;
+    if constexpr (SORTED) {
+      if (a.full)
+        wfull = __builtin_amdgcn_ballot_w64(act && (g0 < 15 ? pb0 == 0xFFFFu : grid_skip(mw) == 0u)) == ~0ull;
     }
-    const int n = gcount(pb);
+    // one source for both forms (the rest of the iteration, at its old indentation)
+    auto body = [&](auto full_c) {
+    constexpr bool FULL = decltype(full_c)::value;
+    // FULL takes the lane ids and the stock index through an empty asm, as values of its
+    // own: what the two forms derive from them (LDS slots, key bytes, lane masks, store
+    // addresses) is otherwise computed once in front of the branch and stays live through
+    // the body (spills).  The general form keeps the plain values, so it compiles to the
+    // code it was before there were two forms.
+    int g = g0, gb = gbase(), si = wave * 4 + grp, sl = act ? s : 0;
+    if constexpr (FULL) asm("" : "+v"(g), "+v"(gb), "+v"(si), "+v"(sl));
+    const size_t sd = (size_t)d * a.S + sl;  // = sd0: the day's part stays scalar
+    // (their ranges, which the asm hides)
+    g &= 15;
+    gb &= 48;
+    si &= 15;
+    uint64_t* scr = scratch[si];
+    double* scr_d = reinterpret_cast<double*>(scr);
+    const uint32_t lm = g < 15 ? ~0u : 0u;  // FULL: the lane's presence mask
+    const uint32_t pb = FULL ? (lm & 0xFFFFu) : pb0;
+    auto pres = [&](int k) { return FULL ? lm : present_bits(pb, k); };
+    auto absn = [&](int k) { return FULL ? ~lm : absent_bits(pb, k); };
+    const int n = FULL ? NBAR : gcount(pb);
     Res R;
     R.r[0] = R.r[1] = R.r[2] = R.r[3] = 0.0;
     R.st = 0u;
@@ -259,8 +290,10 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
             const uint4 t = p4[q];
             x[4 * q + 0] = t.x; x[4 * q + 1] = t.y; x[4 * q + 2] = t.z; x[4 * q + 3] = t.w;
           }
+          if constexpr (!FULL) {
 #pragma unroll
-          for (int k = 0; k < K; ++k) x[k] &= present_bits(pb, k);
+            for (int k = 0; k < K; ++k) x[k] &= present_bits(pb, k);
+          }
         } else {
 #pragma unroll
           for (int k = 0; k < K; ++k) x[k] = 0u;
@@ -282,7 +315,7 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
         sanitize(h, 1.0f);
         sanitize(lo, 1.0f);
       }
-      const int fb = gfirst(pb), lb = glast(pb);
+      const int fb = FULL ? 0 : gfirst(pb), lb = FULL ? NBAR - 1 : glast(pb);
 
       // ================================================================ OLS CM:93-376
       if (fam & F_OLS) {
@@ -464,7 +497,7 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
 
         uint32_t key[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) key[k] = v[k] | absent_bits(pb, k);  // v sanitized; < 2^32 - 1
+        for (int k = 0; k < K; ++k) key[k] = v[k] | absn(k);  // v sanitized; < 2^32 - 1
         gsort256u(key);
         // the sorted keys go through the group's LDS scratch (element e = 16 g + k at slot
         // 16 k + g: conflict-free stores), and each lane reads the one element it needs:
@@ -804,15 +837,17 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
         uint32_t cmx = 0u, cmn = 0xffffffffu;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-          cmx = max(cmx, fbits(c[k]) & present_bits(pb, k));
-          cmn = min(cmn, fbits(c[k]) | absent_bits(pb, k));
+          cmx = max(cmx, fbits(c[k]) & pres(k));
+          cmn = min(cmn, fbits(c[k]) | absn(k));
         }
         // the level volumes below are exact u32 cumulative sums: a day whose volume
         // reaches 2^32 shares goes to the exact kernel (f64 sums, exact below 2^53)
         const bool ok = sumv < 4294967296.0;
         cmx = gmax_u(cmx);
         cmn = gmin_u(cmn);
-        const float clastf = gval(c, lb);
+        float clastf;
+        if constexpr (FULL) clastf = gvalc<NBAR - 1>(c);
+        else clastf = gval(c, lb);
         bool fast = !gany(!ok);
         const int e0 = 16 * g;
         uint32_t cw[K], vv[K], cbase = cmx;
@@ -837,7 +872,7 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
           for (int k = 0; k < K; ++k) {
             const uint32_t slot = (uint32_t)(16 * k + g);
             sv[slot] = v[k];  // absent bars hold 0 (sanitized)
-            key[k] = ((cmx - fbits(c[k])) << 8) | slot | absent_bits(pb, k);
+            key[k] = ((cmx - fbits(c[k])) << 8) | slot | absn(k);
           }
           gsort256u(key);
           lds_fence();
@@ -967,7 +1002,7 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
     // (mask word 7): none, or every one (its mask words are zero: n == 0 above), or for a
     // kept stock-day the families that read a field holding a null -- their stores, and
     // with doc_pdf its levels and queries, are left to mff_stage1_rows
-    const uint32_t skip = act ? grid_skip(a.mask[sd * 8 + 7]) : 0u;
+    const uint32_t skip = (!FULL && act) ? grid_skip(a.mask[sd * 8 + 7]) : 0u;
     if (skip & F_PDF) emitL = 0u;
     const bool emit = a.lvl_key != nullptr;  // uniform
     uint32_t lpreA = 0u, lpreB = 0u, gA = 0u;
@@ -1048,6 +1083,13 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
         wd[at] = (uint8_t)(ee - ep);
       }
       lds_fence();  // the next iteration rewrites the scratch
+    }
+    };  // body
+    if constexpr (SORTED) {
+      if (wfull) body(std::true_type());
+      else body(std::false_type());
+    } else {
+      body(std::false_type());
     }
   }
 }
@@ -1134,6 +1176,8 @@ static int stage1_parts(const float* open, const float* high, const float* low, 
   a.fb_count = cnt;
   a.fb_list = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + 256);
   a.ord_th = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + 256 + (size_t)S * D * sizeof(int));
+  const char* fullenv = getenv("MFF_STAGE1G_FULL");  // "0": the general form for every wave (test hook)
+  a.full = !(fullenv && strcmp(fullenv, "0") == 0);
   const char* impl = getenv("MFF_STAGE1_IMPL");
   const bool w64 = impl && strcmp(impl, "w64") == 0;
   const long long nblk = (long long)((S + 16 * kGIter - 1) / (16 * kGIter)) * D;
