@@ -566,6 +566,81 @@ int mff_xs_orth_apply(const double* x_val, const uint8_t* x_state, int K, int D,
                       void* stream);
 
 /*
+ * Composite factor: K factors' exposures combined into one signal with equal, rolling-IC,
+ * rolling-ICIR or max-ICIR weights.  No reference function (Factor.py never combines
+ * factors); this is the build's definition, restated in numpy by
+ * tests/xs_combine_ref.py.
+ *   Inputs: x [K][D][S] (val f64, state u8), 1 <= K <= 64; y [Ky][D][S] (val, state), the
+ *   forward return: Ky = 1 pairs every factor with row 0 (Pearson IC), Ky = K pairs row k with
+ *   row k (rank IC: x and y are then the average ranks over the pair set, mff_ic_pairs +
+ *   mff_xs_rank per factor), Ky = 0 with y NULL = no y (the pair moments are 0, every IC NaN).
+ *   Below h = future_days >= 1, W = window >= 1, m = min_periods >= 1.
+ * moments: one pass over x and y -> partial f64 [K][D][9] = (n_x, mean_x, M2_x, n_p, mean_xp,
+ *   mean_yp, Cxx, Cyy, Cxy) of the local S stocks.
+ *     z set (the first three): x VALUE and finite (the set of mff_xs_moments).
+ *     pair set (the last six): x VALUE and not NaN, y VALUE (the rule of mff_ic_pairs); a
+ *       non-finite x or y inside the pair set makes the date's IC NaN, as there.
+ *     Centred moments, never raw power sums: per 512-stock chunk the values are shifted by the
+ *       chunk's first included value (that value's finite part for the pairs), the mean taken,
+ *       then the centred squares and products (the two passes of mff_ic_moments on registers);
+ *       chunks are merged in stock order by the pairwise update n = na + nb, dl = mean_b - mean_a,
+ *       M2 += M2_b + dl^2 na nb / n, mean += dl nb / n.  A constant set gives M2 = 0 exactly.
+ *     Each stock tile of y is read once for all K factors of a day (Ky = 1); neither x nor y is
+ *     read more than once.
+ * finalize: merges the R shards' partials [R][K][D][9] by the same update in rank order and
+ *   writes zmom f64 [K][D][3] = (n, mean, std with ddof = 1): std NaN when n < 2, a std of 0 is
+ *   kept as 0 and means "z undefined"; ic f64 [K][D] = Cxy / sqrt(Cxx Cyy), NaN when
+ *   n_p < max(2, min_obs) or the denominator is 0 (the rule of mff_ic_finalize);
+ *   n_pairs int32 [K][D] = n_p, always written and exact.
+ * weights: ic [K][D] -> weights f64 [D][K], count int32 [D][K], status int32 [D] (0 ok, 1 too
+ *   little history, 2 singular or degenerate).  For date index d the window is
+ *   E(d) = {e : max(0, d - h - W + 1) <= e <= d - h}, empty when d < h: only ICs whose return
+ *   horizon has closed by d are used (no look-ahead).
+ *     equal (0): w_raw[k] = 1; count 0, status 0; ic may be NULL.
+ *     ic (1): c_k = the finite ic[k][e] in E(d); w_raw[k] = their mean when c_k >= m, else 0.
+ *     icir (2): needs c_k >= max(m, 2) and a std (ddof = 1) finite and > 0: w_raw[k] = mean /
+ *       std, else 0.  For ic and icir count[d][k] = c_k, and status 1 when no factor qualifies.
+ *       Means and stds run in date order on values shifted by the window's first finite IC, so
+ *       a constant IC series has std = 0 exactly.
+ *     max_icir (3): L(d) = the dates of E(d) on which all K ICs are finite, c = |L| in every
+ *       column of count.  Status 1 unless c >= max(m, 2) and, when shrink == 0, c >= K + 1.
+ *       mu and Sigma (ddof = 1) over L; Sigma_s = (1 - shrink) Sigma + shrink diag(Sigma),
+ *       0 <= shrink <= 1; w_raw = Sigma_s^-1 mu.  Pivot rule (that of mff_xs_orth_solve /
+ *       mff_xs_reg_solve): a Sigma_ii that is not > 0 is status 2; otherwise Sigma_s is scaled
+ *       to a unit diagonal, C_ij = (1 - shrink) Sigma_ij / sqrt(Sigma_ii Sigma_jj), factored by
+ *       an unpivoted f64 Cholesky, and a pivot <= 1e-10 is status 2; C u = mu / sigma,
+ *       w_raw = u / sigma.
+ *     Then w = w_raw / sum_k |w_raw[k]|; a sum that is zero or not finite is status 2.  On
+ *     status != 0 the weights row is NaN.  One wave per date.
+ * apply: x, zmom, weights, status -> the composite [D][S] (val, state).
+ *     z[k][d][s] = (x - mean) / std where x is VALUE and finite, n >= 2 and std > 0 (computed
+ *       as (x - mean) * (1 / std)).
+ *     P(d, s) = the k with z defined and weights[d][k] != 0.
+ *     status[d] == 0 and |P| >= min_factors (1 <= min_factors <= K):
+ *       val = sum_P w z / sum_P |w|, both sums in factor order, state VALUE: the weights are
+ *       renormalised over the factors a stock actually has.
+ *     Otherwise val = 0.0; state ABSENT when every x[k][d][s] is ABSENT, else NULL.
+ *   The result is bit-identical from run to run (fixed summation orders: the lane tree of a
+ *   chunk, chunk order, rank order, date order, factor order; no floating-point atomics).
+ * Errors (negative, nothing launched, nothing written): K < 1, K > 64, a negative size, Ky not
+ * 0 / 1 / K or not matching y, R < 1, min_obs < 0, method outside 0..3, future_days / window /
+ * min_periods < 1, shrink outside [0, 1] (NaN included), min_factors outside [1, K].  D == 0 is
+ * a success (nothing written); S == 0 is a success (moments: all-zero partials; apply: nothing
+ * written).
+ */
+int mff_xs_comb_moments(const double* x_val, const uint8_t* x_state, int K, int D, int S,
+                        const double* y_val, const uint8_t* y_state, int Ky, double* partial,
+                        void* stream);
+int mff_xs_comb_finalize(const double* partial_all /* [R][K][D][9] */, int R, int K, int D,
+                         int min_obs, double* zmom, double* ic, int32_t* n_pairs, void* stream);
+int mff_xs_comb_weights(const double* ic, int K, int D, int method, int future_days, int window,
+                        int min_periods, double shrink, double* weights, int32_t* count,
+                        int32_t* status, void* stream);
+int mff_xs_comb_apply(const double* x_val, const uint8_t* x_state, int K, int D, int S,
+                      const double* zmom, const double* weights, const int32_t* status,
+                      int min_factors, double* out_val, uint8_t* out_state, void* stream);
+
+/*
  * Factor IC / rank-IC test.  Replaces Factor.ic_test
  * (Factor.py:127-229).  Inputs are dense [D][S] (val, state) like stage 1's output rows.
  * mff_future_return: Factor.py:142-162 — per stock over its present days,

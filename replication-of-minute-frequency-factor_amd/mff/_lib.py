@@ -74,6 +74,10 @@ SIGNATURES = {
     "mff_xs_orth_gram": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
     "mff_xs_orth_solve": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "mff_xs_orth_apply": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P]),
+    "mff_xs_comb_moments": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P]),
+    "mff_xs_comb_finalize": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "mff_xs_comb_weights": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, P, P, P, P]),
+    "mff_xs_comb_apply": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P]),
     "mff_future_return": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "mff_ic_pairs": (c_int, [P, P, P, P, c_int, c_int, P, P, P]),
     "mff_ic_moments": (c_int, [P, P, c_int, c_int, P, P]),

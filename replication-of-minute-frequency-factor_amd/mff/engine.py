@@ -1305,6 +1305,133 @@ def factor_orthogonalize(x_val: torch.Tensor, x_state: torch.Tensor, method: str
     return OrthResult(ov, os_, tr, eig, keep, n, status)
 
 
+COMBINE_METHODS = ("equal", "ic", "icir", "max_icir")
+COMBINE_IC = ("pearson", "rank")
+COMBINE_MAX_FACTORS = 64  # K of mff_xs_comb_*
+COMBINE_RANK_BYTES = CORR_PLANE_BYTES  # cap of the ranked (x, y) planes of one day batch (ic='rank')
+
+
+class CombineResult(NamedTuple):
+    """factor_combine: the composite and what it was built from (device tensors)."""
+    val: torch.Tensor      # float64 [D][S_loc]
+    state: torch.Tensor    # uint8 [D][S_loc]
+    weights: torch.Tensor  # float64 [D][K]: sum_k |w| = 1; NaN on a date with status != 0
+    ic: torch.Tensor       # float64 [K][D]: per-date IC (Pearson or rank) of every factor
+    n_pairs: torch.Tensor  # int32 [K][D]
+    count: torch.Tensor    # int32 [D][K]: usable window dates behind each weight
+    status: torch.Tensor   # int32 [D]: 0 ok, 1 too little history, 2 singular or degenerate
+
+
+def _int_arg(name: str, v, lo: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def _comb_moments(lib, xv, xs, yv, ys, Ky, min_obs, comm, st):
+    """mff_xs_comb_moments + the shards' partials gathered + mff_xs_comb_finalize ->
+    (zmom [K][D][3], ic [K][D], n_pairs [K][D])."""
+    K, D, S = xv.shape
+    dev = xv.device
+    R = 1 if comm is None else comm.world_size
+    part = torch.empty((K, D, 9), dtype=torch.float64, device=dev)
+    _lib.check(lib.mff_xs_comb_moments(_lib.ptr(xv), _lib.ptr(xs), K, D, S, _lib.ptr(yv), _lib.ptr(ys), Ky,
+                                       _lib.ptr(part), st), "mff_xs_comb_moments")
+    part_all = part if comm is None else comm.all_gather(part).contiguous()
+    zmom = torch.empty((K, D, 3), dtype=torch.float64, device=dev)
+    ic = torch.empty((K, D), dtype=torch.float64, device=dev)
+    npairs = torch.empty((K, D), dtype=torch.int32, device=dev)
+    _lib.check(lib.mff_xs_comb_finalize(_lib.ptr(part_all), R, K, D, min_obs, _lib.ptr(zmom), _lib.ptr(ic),
+                                        _lib.ptr(npairs), st), "mff_xs_comb_finalize")
+    return zmom, ic, npairs
+
+
+def factor_combine(x_val: torch.Tensor, x_state: torch.Tensor, y_val: Optional[torch.Tensor] = None,
+                   y_state: Optional[torch.Tensor] = None, method: str = "icir", future_days: int = 5,
+                   window: int = 60, min_periods: int = 20, ic: str = "pearson", shrink: float = 0.5,
+                   min_obs: int = 0, min_factors: int = 1, comm=None,
+                   stocks_total: Optional[int] = None) -> CombineResult:
+    """One composite [D][S_loc] from the K exposure rows x [K][D][S_loc] (mff_xs_comb_*; the
+    definition is on the declarations in include/mff.h): per date every factor's z-score,
+    weighted by ``method`` -- 'equal', or from the factor's ICs against the forward return y
+    [D][S_loc] over the trailing ``window`` dates whose ``future_days`` horizon has closed:
+    'ic' (mean IC), 'icir' (mean / std), 'max_icir' (Sigma_s^-1 mu with the off-diagonal of the
+    IC covariance shrunk by ``shrink``) -- and renormalised per stock over the factors it has
+    (at least ``min_factors`` of them, else null).
+
+    ``ic``: 'pearson', or 'rank' (per factor mff_ic_pairs then the stage-3 rank of the pair
+    set, in day batches of at most COMBINE_RANK_BYTES of ranked planes).  ``min_periods``: the
+    finite ICs a window needs; ``min_obs``: the pairs a date's IC needs (at least 2).  y may be
+    None for 'equal' (every IC is then NaN).
+
+    Stock-sharded (``comm``): the moment partials are all-gathered and merged in rank order,
+    the weights are computed on every rank, the apply pass is local."""
+    lib = _lib.load()
+    if x_val.dim() != 3 or x_state.shape != x_val.shape:
+        raise ValueError("x_val and x_state must be [K][D][S]")
+    K, D, S = x_val.shape
+    if K < 1 or K > COMBINE_MAX_FACTORS:
+        raise _lib.MffError(f"factor_combine: K={K} outside [1, {COMBINE_MAX_FACTORS}]")
+    if method not in COMBINE_METHODS:
+        raise ValueError(f"method must be one of {COMBINE_METHODS}, got {method!r}")
+    if ic not in COMBINE_IC:
+        raise ValueError(f"ic must be one of {COMBINE_IC}, got {ic!r}")
+    future_days = _int_arg("future_days", future_days, 1)
+    window = _int_arg("window", window, 1)
+    min_periods = _int_arg("min_periods", min_periods, 1)
+    min_obs = _int_arg("min_obs", min_obs, 0)
+    min_factors = _int_arg("min_factors", min_factors, 1)
+    if min_factors > K:
+        raise ValueError(f"min_factors must be at most the number of factors {K}, got {min_factors!r}")
+    if isinstance(shrink, bool) or not isinstance(shrink, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(shrink) <= 1.0:
+        raise ValueError(f"shrink must be a number in [0, 1], got {shrink!r}")
+    if (y_val is None) != (y_state is None):
+        raise ValueError("y_val and y_state go together")
+    if y_val is None and method != "equal":
+        raise ValueError(f"method {method!r} needs the forward return y")
+    if y_val is not None and (tuple(y_val.shape) != (D, S) or y_state.shape != y_val.shape):
+        raise ValueError("y_val and y_state must be [D][S]")
+    dev = x_val.device
+    st = _stream(dev)
+    f64, u8 = torch.float64, torch.uint8
+    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
+    if y_val is not None:
+        y_val, y_state = y_val.to(f64).contiguous(), y_state.to(u8).contiguous()
+    zmom, ics, npairs = _comb_moments(lib, x_val, x_state, y_val, y_state, 0 if y_val is None else 1, min_obs,
+                                      comm, st)
+    if ic == "rank" and y_val is not None and D > 0 and S > 0:
+        S_w = S if comm is None else shard_width(comm, S, stocks_total, dev)  # the same batches on every rank
+        nd_max = max(1, COMBINE_RANK_BYTES // (2 * K * S_w * 9))
+        for d0 in range(0, D, nd_max):
+            nd = min(nd_max, D - d0)
+            rv = torch.empty((2, K, nd, S), dtype=f64, device=dev)
+            rs = torch.empty((2, K, nd, S), dtype=u8, device=dev)
+            pv = torch.empty((2, nd, S), dtype=f64, device=dev)
+            ps = torch.empty((2, nd, S), dtype=u8, device=dev)
+            yv, ys = y_val[d0:d0 + nd], y_state[d0:d0 + nd]
+            for k in range(K):
+                xv, xs = x_val[k, d0:d0 + nd], x_state[k, d0:d0 + nd]
+                _lib.check(lib.mff_ic_pairs(_lib.ptr(xv), _lib.ptr(xs), _lib.ptr(yv), _lib.ptr(ys), nd, S,
+                                            _lib.ptr(pv), _lib.ptr(ps), st), "mff_ic_pairs")
+                kv, ks = cross_section(pv, ps, "rank", comm=comm, stocks_total=stocks_total)
+                rv[:, k], rs[:, k] = kv, ks
+            _, ic_b, _ = _comb_moments(lib, rv[0], rs[0], rv[1], rs[1], K, min_obs, comm, st)
+            ics[:, d0:d0 + nd] = ic_b
+    weights = torch.empty((D, K), dtype=f64, device=dev)
+    count = torch.empty((D, K), dtype=torch.int32, device=dev)
+    status = torch.empty(D, dtype=torch.int32, device=dev)
+    _lib.check(lib.mff_xs_comb_weights(_lib.ptr(ics), K, D, COMBINE_METHODS.index(method), future_days, window,
+                                       min_periods, float(shrink), _lib.ptr(weights), _lib.ptr(count),
+                                       _lib.ptr(status), st), "mff_xs_comb_weights")
+    ov = torch.empty((D, S), dtype=f64, device=dev)
+    os_ = torch.empty((D, S), dtype=u8, device=dev)
+    _lib.check(lib.mff_xs_comb_apply(_lib.ptr(x_val), _lib.ptr(x_state), K, D, S, _lib.ptr(zmom), _lib.ptr(weights),
+                                     _lib.ptr(status), min_factors, _lib.ptr(ov), _lib.ptr(os_), st),
+               "mff_xs_comb_apply")
+    return CombineResult(ov, os_, weights, ics, npairs, count, status)
+
+
 def future_return(pct_val: torch.Tensor, pct_state: torch.Tensor, N: int):
     """Factor.py:142-162 on dense [D][S] daily pct_change rows: compounded return of the
     next N present days per stock (mff_future_return).  Returns (val, state) [D][S]."""

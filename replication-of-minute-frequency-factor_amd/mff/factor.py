@@ -341,6 +341,20 @@ class Factor:
         out = orthogonalize(group, method="schmidt", **kw)
         return out[self.factor_name]
 
+    def combine_with(self, others, **kw):
+        """:func:`combine` of ``[self, *others]`` (``others``: a Factor, a sequence of them or a
+        mapping name -> Factor; keywords as there): the composite :class:`Factor`, with
+        ``return_info`` followed by the weights and IC frames."""
+        if isinstance(others, Factor):
+            others = [others]
+        if isinstance(others, dict):
+            if self.factor_name in others:
+                raise ValueError(f"duplicate factor name {self.factor_name!r}")
+            group = {self.factor_name: self, **others}
+        else:
+            group = [self] + list(others)
+        return combine(group, **kw)
+
 
 def _industry_ids(industry, codes, dates):
     """``industry`` (None, or a long frame [code, industry] / [code, date, industry]; labels of
@@ -540,6 +554,90 @@ def orthogonalize(factors, method: str = "symmetric", min_obs: Optional[int] = N
                                "mean_keep": ok.mean(axis=0) if days else np.full(K, np.nan),
                                "min_keep": ok.min(axis=0) if days else np.full(K, np.nan)}, index=list(names))
     return out, per_date, per_factor
+
+
+def combine(factors, method: str = "icir", future_days: int = 5, window: int = 60, min_periods: int = 20,
+            ic: str = "pearson", shrink: float = 0.5, min_factors: int = 1, name: str = "composite",
+            return_info: bool = False, pv_data=None, device=None):
+    """One composite factor from several factors' exposures on the GPU (mff_xs_comb_*,
+    include/mff.h): per date every factor's cross-sectional z-score, weighted and summed per
+    code over the factors that code has (at least ``min_factors`` of them, else null; the
+    weights are renormalised over those).  No reference counterpart: Factor.py never combines
+    factors.
+
+    ``method``: 'equal'; 'ic' (the factor's mean IC against the ``future_days`` compounded
+    return over the trailing ``window`` dates whose horizon has closed -- no look-ahead);
+    'icir' (mean / std of those ICs); 'max_icir' (Sigma_s^-1 mu of the factors' IC means and
+    covariance over the dates where all have an IC, the off-diagonal shrunk by ``shrink`` in
+    [0, 1]).  A factor with fewer than ``min_periods`` ICs in the window gets weight 0; a date
+    where none qualifies, or whose covariance is singular, has no composite.  ``ic``:
+    'pearson' or 'rank'.
+
+    ``factors``: a sequence of :class:`Factor` or a mapping name -> Factor (duplicate names
+    raise ValueError); the universe is the union of their codes and dates and, unless
+    ``method='equal'`` (which reads no ``pv_data``), of ``pv_data`` (default: the daily
+    price-volume file; columns code, date, pct_change).
+
+    Returns a :class:`Factor` named ``name`` holding [code, date, ``name``]; the inputs are
+    untouched.  With ``return_info=True`` also a weights frame [date, status, <one column per
+    factor>] and an IC frame [date, <one column per factor>], as a tuple."""
+    import torch
+
+    from . import engine
+    from .factors import _device
+
+    pd = _pd()
+    if method not in engine.COMBINE_METHODS:
+        raise ValueError(f"method must be one of {engine.COMBINE_METHODS}, got {method!r}")
+    if ic not in engine.COMBINE_IC:
+        raise ValueError(f"ic must be one of {engine.COMBINE_IC}, got {ic!r}")
+    for what, v, lo in (("future_days", future_days, 1), ("window", window, 1), ("min_periods", min_periods, 1),
+                        ("min_factors", min_factors, 1)):
+        engine._int_arg(what, v, lo)
+    if isinstance(shrink, bool) or not isinstance(shrink, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(shrink) <= 1.0:
+        raise ValueError(f"shrink must be a number in [0, 1], got {shrink!r}")
+    if not isinstance(name, str) or not name:
+        raise ValueError(f"name must be a non-empty string, got {name!r}")
+    names, objs = _named_factors(factors, "combine")
+    if return_info and {"date", "status"} & set(names):
+        raise ValueError("a factor named 'date' or 'status' collides with the columns of the info frames")
+    if min_factors > len(objs):
+        raise ValueError(f"min_factors must be at most the number of factors {len(objs)}, got {min_factors!r}")
+    if len(objs) > engine.COMBINE_MAX_FACTORS:
+        raise ValueError(f"combine takes at most {engine.COMBINE_MAX_FACTORS} factors, got {len(objs)}")
+    exposures = [f.factor_exposure for f in objs]
+    pv = None
+    if method != "equal":
+        need = ["code", "date", "pct_change"]
+        pv = pv_data if pv_data is not None else Factor._read_daily_pv_data(need)
+        for c in need:
+            if c not in pv.columns:
+                raise ValueError(f"pv_data has no column {c!r}")
+    codes, dates = frames.universe(*exposures, pv) if pv is not None else frames.universe(*exposures)
+    K, D, S = len(objs), len(dates), len(codes)
+    val = np.zeros((K, D, S), dtype=np.float64)
+    state = np.zeros((K, D, S), dtype=np.uint8)
+    for i, (f, ex) in enumerate(zip(objs, exposures)):
+        val[i], state[i], _, _ = frames.from_long(ex, f.factor_name, codes=codes, dates=dates)
+    dev = _device(device)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    yv = ys = None
+    if pv is not None:
+        pc_v, pc_s, _, _ = frames.from_long(pv, "pct_change", codes=codes, dates=dates)
+        yv, ys = engine.future_return(t(pc_v), t(pc_s), future_days)
+    res = engine.factor_combine(t(val), t(state), yv, ys, method=method, future_days=int(future_days),
+                                window=int(window), min_periods=int(min_periods), ic=ic, shrink=float(shrink),
+                                min_factors=int(min_factors))
+    torch.cuda.synchronize(dev)
+    out = Factor(name, frames.to_long(res.val.cpu().numpy(), res.state.cpu().numpy(), codes, dates, name))
+    if not return_info:
+        return out
+    dd = np.asarray(dates, dtype=object)
+    w, icv = res.weights.cpu().numpy(), res.ic.cpu().numpy()
+    wf = pd.DataFrame({"date": dd, "status": res.status.cpu().numpy(), **{nm: w[:, k] for k, nm in enumerate(names)}})
+    icf = pd.DataFrame({"date": dd, **{nm: icv[k] for k, nm in enumerate(names)}})
+    return out, wf, icf
 
 
 def factor_correlation(factors, method: str = "pearson", min_pairs: int = 2, return_daily: bool = False,
