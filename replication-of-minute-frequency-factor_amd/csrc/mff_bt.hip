@@ -52,8 +52,13 @@ struct BtLoader {
 };
 
 // numpy.quantile(method='linear') of sorted[0..n) at q (numpy/lib/_function_base_impl.py
-// _quantile: virtual index (n-1)*q, floor / +1 clipped to n-1, _lerp two-sided)
+// _quantile: virtual index (n-1)*q, floor / +1 clipped to n-1, _lerp two-sided).
+// Uncontracted: numpy rounds the product (n-1)*q before it takes gamma, so an index that
+// rounds to an integer gives gamma = 0 and an edge equal to a data value; an FMA would
+// take gamma from the unrounded product, put the edge an ulp beside that value and move
+// the stock on it to the next bin.
 __device__ double np_quantile(const uint64_t* sorted, int n, double q) {
+#pragma clang fp contract(off)
   const double virt = (double)(n - 1) * q;
   const double prev = floor(virt);
   const double gamma = virt - prev;

@@ -181,8 +181,8 @@ def test_qcut_kernel_formula_matches_pandas():
     random columns of many sizes and group counts."""
     rng = np.random.default_rng(11)
     for trial in range(400):
-        n = int(rng.integers(1, 120))
-        G = int(rng.integers(1, 12))
+        n = int(rng.integers(1, 400))
+        G = int(rng.integers(1, 64))
         x = np.round(rng.normal(size=n), int(rng.integers(0, 3)))
         ok = rng.random(n) > 0.1
         assert np.array_equal(_qcut_kernel_formula(x, ok, G), O.oracle_qcut(x, ok, G)), (trial, n, G)
