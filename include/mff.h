@@ -317,6 +317,17 @@ int mff_xs_zscore(const double* val, const uint8_t* state, int rows, int D, int 
 int mff_xs_zscore_local(const double* val, const uint8_t* state, int rows, int D, int S,
                         double* out_val, uint8_t* out_state, void* stream);
 int mff_xs_zscore_local_max_stocks(void);
+/* Rank workspace layout, with nseg = rows * D, M = R * S_all, g = min(nseg, 2048):
+ *   [0, sort)          the sorting kernel's buffers: sort = 256 bytes (unused) when
+ *                      M <= 8192 (the sort runs in LDS), else g * 2 * M * 8 bytes (two u64
+ *                      [M] ping-pong buffers per workgroup);
+ *   [sort, sort + lst) the hand-over list, uint32 [1 + nseg]: word 0 = the number of
+ *                      (row, day) segments the bucketed kernels handed to the sorting kernel
+ *                      in this call, then their segment indices (row * D + day) in no
+ *                      particular order; lst = 4 * (nseg + 1) rounded up to 256.
+ * The list is written only when M <= 8192 and the bucketed kernels run (not under
+ * MFF_XS_RANK_IMPL=sort); otherwise its bytes are left untouched.  The count is valid once
+ * the call's stream work has completed. */
 size_t mff_xs_rank_workspace_bytes(int rows, int D, int S_all, int R);
 int mff_xs_rank(const double* val, const uint8_t* state, int rows, int D, int S_loc,
                 const double* val_all, const uint8_t* state_all, int R, int S_all,
