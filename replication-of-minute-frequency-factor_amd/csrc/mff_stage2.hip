@@ -30,8 +30,10 @@ namespace mff {
 // over days; the row leaving the window is re-read from HBM / cache at the `lag` cursor
 // (the day of the window's oldest row; it advances over absent days).  Window state:
 //  * S1 = sum (x - c), S2 = sum (x - c)^2 over the window's finite non-null values as
-//    double-doubles (mff_dd.h), c = the first finite value entering an empty window; a
-//    value leaves with the same shifted image it entered with, so it cancels exactly
+//    double-doubles (mff_dd.h), c = the first finite value entering an empty window; x - c
+//    itself is an exact double-double (c may be far from the window: a rounded x - c would
+//    carry an error of the size of |x - c|, not of the window's range); a value leaves
+//    with the same shifted image it entered with, so it cancels exactly
 //  * counts of nulls (min_samples=N: any null -> null), NaN, +inf, -inf in the window:
 //    a window holding a non-finite value has mean NaN / +-inf and std NaN, as the
 //    from-scratch two-pass gives (so NaN/inf affect only the windows holding them)
@@ -42,6 +44,25 @@ namespace mff {
 // sums are rebuilt from the window's rows with a fresh shift, so the outlier's rounding
 // residue cannot swamp the remaining values.
 constexpr int S2_SLIDE_THREADS = 256;
+
+// Mean and std of a window from its shifted sums.  The shift c may lie far from the window
+// (it is the first value that entered, rows ago), so nothing here is rounded at the size of
+// |x - c|: the shifted images are exact double-doubles (dd_diff), S1 / N stays a
+// double-double until c is added, and one rounding is left at the size of the mean itself.
+__device__ __forceinline__ void slide_stats(DD S1, DD S2, double c, int N, double& mean, double& sd) {
+  const DD m1 = dd_div(S1, (double)N);
+  double s, e;
+  two_sum(c, m1.hi, s, e);
+  mean = s + (e + m1.lo);
+  const DD q = dd_add(S2, dd_neg(dd_sq_div(S1, (double)N)));
+  const double var = q.hi + q.lo;
+  sd = sqrt(var > 0.0 ? var / (double)N : 0.0);
+}
+// (x - mean) / sd with x - mean = (x - c) - S1 / N taken in double-double
+__device__ __forceinline__ double slide_z(DD S1, double x, double c, int N, double sd) {
+  const DD dz = dd_add(dd_diff(x, c), dd_neg(dd_div(S1, (double)N)));
+  return (dz.hi + dz.lo) / sd;
+}
 
 __global__ __launch_bounds__(S2_SLIDE_THREADS) void k_stage2_slide(const double* val, const uint8_t* state, int D,
                                                                    int S, int N, int method, double* out_val,
@@ -73,9 +94,9 @@ __global__ __launch_bounds__(S2_SLIDE_THREADS) void k_stage2_slide(const double*
       const double xe = X(e);
       if (!__builtin_isfinite(xe)) continue;
       if (!have) { c = xe; have = true; }
-      const double y = xe - c;
+      const DD y = dd_diff(xe, c);
       S1 = dd_add(S1, y);
-      S2 = dd_add(S2, two_prod(y, y));
+      S2 = dd_add(S2, dd_sq(y));
     }
   };
   for (int d = 0; d < D; ++d) {
@@ -108,11 +129,10 @@ __global__ __launch_bounds__(S2_SLIDE_THREADS) void k_stage2_slide(const double*
         else if (xo == -__builtin_inf()) --nni;
         else {
           --nfin;
-          const double y = xo - c;
+          const DD y = dd_diff(xo, c);
           const double before = S2.hi;
-          S1 = dd_add(S1, -y);
-          const DD p = two_prod(y, y);
-          S2 = dd_add(S2, dd_neg(p));
+          S1 = dd_add(S1, dd_neg(y));
+          S2 = dd_add(S2, dd_neg(dd_sq(y)));
           if (nfin > 0 && before > 0.0 && !(S2.hi > before * 0x1p-30)) {
             do { ++lag; } while (ST(lag) == MFF_STATE_ABSENT);
             rebuild(d);
@@ -137,9 +157,9 @@ __global__ __launch_bounds__(S2_SLIDE_THREADS) void k_stage2_slide(const double*
         S2 = DD{0.0, 0.0};
       }
       ++nfin;
-      const double y = x - c;
+      const DD y = dd_diff(x, c);
       S1 = dd_add(S1, y);
-      S2 = dd_add(S2, two_prod(y, y));
+      S2 = dd_add(S2, dd_sq(y));
     }
     ++k;
     if (cnt < N || nnull > 0) {
@@ -158,14 +178,9 @@ __global__ __launch_bounds__(S2_SLIDE_THREADS) void k_stage2_slide(const double*
       mean = x;
       sd = 0.0;
     } else {
-      const double inv_n = 1.0 / (double)N;
-      const double m1 = (S1.hi + S1.lo) * inv_n;
-      mean = c + m1;
-      const DD q = dd_add(S2, dd_neg(dd_sq_div(S1, (double)N)));
-      const double var = q.hi + q.lo;
-      sd = sqrt(var > 0.0 ? var * inv_n : 0.0);
+      slide_stats(S1, S2, c, N, mean, sd);
       if (method == MFF_ROLL_Z) {
-        ov[o] = (((x - c) - m1)) / sd;
+        ov[o] = slide_z(S1, x, c, N, sd);
         os[o] = MFF_STATE_VALUE;
         continue;
       }
@@ -216,9 +231,9 @@ __global__ __launch_bounds__(64) void k_stage2_ring(const double* val, const uin
       const double xe = __longlong_as_double((long long)b);
       if (!__builtin_isfinite(xe)) continue;
       if (!have) { c = xe; have = true; }
-      const double y = xe - c;
+      const DD y = dd_diff(xe, c);
       S1 = dd_add(S1, y);
-      S2 = dd_add(S2, two_prod(y, y));
+      S2 = dd_add(S2, dd_sq(y));
     }
   };
   auto day = [&](double x, uint8_t sx, size_t o) {
@@ -250,10 +265,10 @@ __global__ __launch_bounds__(64) void k_stage2_ring(const double* val, const uin
         else if (xo == -__builtin_inf()) --nni;
         else {
           --nfin;
-          const double y = xo - c;
+          const DD y = dd_diff(xo, c);
           const double before = S2.hi;
-          S1 = dd_add(S1, -y);
-          S2 = dd_add(S2, dd_neg(two_prod(y, y)));
+          S1 = dd_add(S1, dd_neg(y));
+          S2 = dd_add(S2, dd_neg(dd_sq(y)));
           rb = nfin > 0 && before > 0.0 && !(S2.hi > before * 0x1p-30);
         }
       }
@@ -274,9 +289,9 @@ __global__ __launch_bounds__(64) void k_stage2_ring(const double* val, const uin
       }
       ++nfin;
       if (!rb) {
-        const double y = x - c;
+        const DD y = dd_diff(x, c);
         S1 = dd_add(S1, y);
-        S2 = dd_add(S2, two_prod(y, y));
+        S2 = dd_add(S2, dd_sq(y));
       }
     }
     if (rb) rebuild();
@@ -297,14 +312,9 @@ __global__ __launch_bounds__(64) void k_stage2_ring(const double* val, const uin
       mean = x;
       sd = 0.0;
     } else {
-      const double inv_n = 1.0 / (double)N;
-      const double m1 = (S1.hi + S1.lo) * inv_n;
-      mean = c + m1;
-      const DD q = dd_add(S2, dd_neg(dd_sq_div(S1, (double)N)));
-      const double var = q.hi + q.lo;
-      sd = sqrt(var > 0.0 ? var * inv_n : 0.0);
+      slide_stats(S1, S2, c, N, mean, sd);
       if (method == MFF_ROLL_Z) {
-        ov[o] = ((x - c) - m1) / sd;
+        ov[o] = slide_z(S1, x, c, N, sd);
         os[o] = MFF_STATE_VALUE;
         return;
       }
@@ -697,7 +707,8 @@ extern "C" int mff_stage2(const double* val, const uint8_t* state, int rows, int
   MFF_REQUIRE(rows > 0 && D > 0 && S > 0, "mff_stage2: bad sizes rows=%d D=%d S=%d", rows, D, S);
   MFF_REQUIRE(N >= 1, "mff_stage2: N=%d < 1", N);
   MFF_REQUIRE(method >= MFF_ROLL_O && method <= MFF_ROLL_STD, "mff_stage2: unknown method %d", method);
-  MFF_REQUIRE(val && state && out_val && out_state, "mff_stage2: NULL buffer");
+  MFF_REQUIRE(val && state && out_val && out_state, "mff_stage2: NULL buffer %s",
+              !val ? "val" : !state ? "state" : !out_val ? "out_val" : "out_state");
   // four day segments: more waves in flight for the memory system (a
   // (row, stock) lane per wave-slot otherwise walks all D days: ~4.4 waves per SIMD at c4);
   // each segment of >= 16 N days (a multiple of S2_U) rebuilds its window from the N

@@ -137,6 +137,11 @@ def test_c5_ragged_panel_sampled_and_rolling(dev):
     si = torch.as_tensor(hist, device=dev)
     v1 = val.index_select(0, ri).contiguous()
     s1 = state.index_select(0, ri).contiguous()
+    # ... and against tests/stage2_ref.py inside its f64 error bound, fed the GPU's own stage-1
+    # values of those stocks, so that only stage 2 is judged
+    import stage2_ref
+    ref = stage2_ref.rolling_all(v1.index_select(2, si).cpu().numpy(), s1.index_select(2, si).cpu().numpy(), 20)
+    worst = []
     for meth in ("m", "z", "std"):
         rv, rs = engine.rolling(v1, s1, 20, meth)
         gv = rv.index_select(2, si).cpu().numpy()
@@ -144,4 +149,8 @@ def test_c5_ragged_panel_sampled_and_rolling(dev):
         for r, nm in enumerate(names):
             ev, es = O.oracle_stage2(ov[r], os_[r], 20, meth)
             bad += compare(gv[r], gs[r], ev, es, f"{nm}/20/{meth}", atol=1e-9)
+        b, ratio = stage2_ref.check(gv, gs, ref[meth], f"stage2/20/{meth}/bound")
+        bad += b
+        worst.append(f"{meth} {ratio:.3f}")
+    print("c5 stage 2: worst |gpu - ref| / bound " + ", ".join(worst))
     assert not bad, "\n".join(bad[:30])

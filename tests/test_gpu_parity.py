@@ -249,6 +249,21 @@ def _random_long_panel(D, S, seed):
     return val, state
 
 
+def _s2_bounds(out, v, st, N, tag):
+    """out {method: (gpu val, gpu state)} on (v, st) against tests/stage2_ref.py: states and
+    constant / non-finite windows exact, finite windows inside the reference's f64 error
+    bound.  Prints the worst |error| / bound per method."""
+    import stage2_ref
+    ref = stage2_ref.rolling_all(v, st, N)
+    bad, worst = [], []
+    for meth, (gv, gs) in out.items():
+        b, ratio = stage2_ref.check(gv, gs, ref[meth], f"{tag}/{meth}/bound")
+        bad += b
+        worst.append(f"{meth} {ratio:.3f}")
+    print(f"{tag}: worst |gpu - ref| / bound " + ", ".join(worst))
+    return bad
+
+
 @pytest.mark.parametrize("N,seg", [(3, 4), (20, 12), (20, 40), (64, 8), (64, 100)])
 def test_stage2_day_segments(dev, N, seg, monkeypatch):
     """k_stage2_reg over day segments (MFF_S2_SEG_DAYS): each segment rebuilds its window
@@ -271,12 +286,14 @@ def test_stage2_day_segments(dev, N, seg, monkeypatch):
     state[::9, 13] = 2
     v = np.ascontiguousarray(val[None])
     st = np.ascontiguousarray(state[None])
-    bad = []
+    bad, out = [], {}
     for meth in ("m", "z", "std"):
         rv, rs = engine.rolling(torch.from_numpy(v).to(dev), torch.from_numpy(st).to(dev), N, meth)
         torch.cuda.synchronize()
         ov, os_ = O.oracle_stage2(v[0], st[0], N, meth)
-        bad += compare(rv[0].cpu().numpy(), rs[0].cpu().numpy(), ov, os_, f"N{N}/seg{seg}/{meth}", atol=1e-9)
+        out[meth] = (rv.cpu().numpy(), rs.cpu().numpy())
+        bad += compare(out[meth][0][0], out[meth][1][0], ov, os_, f"N{N}/seg{seg}/{meth}", atol=1e-9)
+    bad += _s2_bounds(out, v, st, N, f"N{N}/seg{seg}")
     assert not bad, "\n".join(bad[:20])
 
 
@@ -297,14 +314,16 @@ def test_stage2_live(dev, N, D):
         val2[20, 6] = 1e15                 # outlier leaving the window (S2 cancellation)
     v = np.ascontiguousarray(np.stack([val, val2]))
     st = np.ascontiguousarray(np.stack([state, state2]))
-    bad = []
+    bad, out = [], {}
     for meth in ("o", "m", "z", "std"):
         rv, rs = engine.rolling(torch.from_numpy(v).to(dev), torch.from_numpy(st).to(dev), N, meth)
         torch.cuda.synchronize()
         rv, rs = rv.cpu().numpy(), rs.cpu().numpy()
+        out[meth] = (rv, rs)
         for r in range(2):
             ov, os_ = O.oracle_stage2(v[r], st[r], N, meth)
             bad += compare(rv[r], rs[r], ov, os_, f"N{N}/D{D}/row{r}/{meth}", atol=1e-9)
+    bad += _s2_bounds(out, v, st, N, f"N{N}/D{D}")
     assert not bad, "\n".join(bad[:20])
 
 
@@ -325,12 +344,14 @@ def test_stage2_chunk_fast_path(dev, N, D):
         val[20, 6] = 1e15
     v = np.ascontiguousarray(val[None])
     st = np.ascontiguousarray(state[None])
-    bad = []
+    bad, out = [], {}
     for meth in ("m", "z", "std"):
         rv, rs = engine.rolling(torch.from_numpy(v).to(dev), torch.from_numpy(st).to(dev), N, meth)
         torch.cuda.synchronize()
         ov, os_ = O.oracle_stage2(v[0], st[0], N, meth)
-        bad += compare(rv[0].cpu().numpy(), rs[0].cpu().numpy(), ov, os_, f"N{N}/D{D}/{meth}", atol=1e-9)
+        out[meth] = (rv.cpu().numpy(), rs.cpu().numpy())
+        bad += compare(out[meth][0][0], out[meth][1][0], ov, os_, f"N{N}/D{D}/{meth}", atol=1e-9)
+    bad += _s2_bounds(out, v, st, N, f"fast N{N}/D{D}")
     assert not bad, "\n".join(bad[:20])
 
 
@@ -344,12 +365,14 @@ def test_stage2_sliding_kernels_forced(dev, impl, N, monkeypatch):
     D = 150
     val, state = _random_long_panel(D, 130, N + 7)
     val[20, 6] = 1e15
-    bad = []
+    bad, out = [], {}
     for meth in ("m", "z", "std"):
         rv, rs = engine.rolling(torch.from_numpy(val[None]).to(dev), torch.from_numpy(state[None]).to(dev), N, meth)
         torch.cuda.synchronize()
         ov, os_ = O.oracle_stage2(val, state, N, meth)
-        bad += compare(rv[0].cpu().numpy(), rs[0].cpu().numpy(), ov, os_, f"{impl}/N{N}/{meth}", atol=1e-9)
+        out[meth] = (rv[0].cpu().numpy(), rs[0].cpu().numpy())
+        bad += compare(out[meth][0], out[meth][1], ov, os_, f"{impl}/N{N}/{meth}", atol=1e-9)
+    bad += _s2_bounds(out, val, state, N, f"{impl}/N{N}")
     assert not bad, "\n".join(bad[:20])
 
 

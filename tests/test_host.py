@@ -66,6 +66,28 @@ def test_library_catalogue_and_errors_without_gpu():
         assert rc < 0 and f"part={part}".encode() in lib.mff_last_error()
 
 
+@pytest.mark.parametrize("case,word", [
+    (dict(rows=0), b"rows=0"), (dict(D=0), b"D=0"), (dict(S=0), b"S=0"), (dict(N=0), b"N=0"),
+    (dict(method=4), b"method 4"), (dict(method=-1), b"method -1"),
+    (dict(out_val=None), b"out_val"), (dict(out_state=None), b"out_state")])
+def test_stage2_argument_guards(case, word):
+    """mff_stage2 refuses empty sizes, N < 1, an unknown method and a NULL output before any
+    device work, names the argument, and leaves the output buffers as they were."""
+    lib = _lib.load()
+    val = np.ones((2, 3, 5))
+    state = np.full((2, 3, 5), 2, np.uint8)
+    ov = np.full((2, 3, 5), -7.0)
+    os_ = np.full((2, 3, 5), 9, np.uint8)
+    a = dict(rows=2, D=3, S=5, N=2, method=1, out_val=ov.ctypes.data, out_state=os_.ctypes.data)
+    a.update(case)
+    rc = lib.mff_stage2(val.ctypes.data, state.ctypes.data, a["rows"], a["D"], a["S"], a["N"], a["method"],
+                        a["out_val"], a["out_state"], None)
+    assert rc < 0
+    msg = lib.mff_last_error()
+    assert msg.startswith(b"mff_stage2") and word in msg, msg
+    assert (ov == -7.0).all() and (os_ == 9).all()
+
+
 def test_mask_roundtrip():
     rng = np.random.default_rng(0)
     pres = rng.random((3, 5, 240)) < 0.7
