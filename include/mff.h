@@ -705,6 +705,71 @@ int mff_bt_reduce(const double* p_ret, const int8_t* p_group, const double* p_we
 int mff_bt_finalize(const double* partial_all, int R, int P, int G, int weighted, double* ret,
                     uint8_t* present, void* stream);
 
+/*
+ * Daily group portfolios: the drifting-weight value of the G quantile portfolios of K factors
+ * per date, and the turnover of every rebalance.  The build's definition; it
+ * extends Factor.group_test (Factor.py:231-350), which keeps one number per period.
+ *
+ * Inputs, dense like mff_bt_*: group int8 [K][D][S] from mff_bt_qcut (-1 = null, else 0..G-1),
+ * x_state u8 [K][D][S]; pct (val, state) [D][S] and an optional weight (val, state) [D][S],
+ * shared by the K factors; period_of int32 [D] on the device, non-decreasing, every period
+ * 0..P-1 present.  1 <= G <= 63, K >= 1.
+ *
+ * Per factor k and stock s, exactly as mff_bt_periods walks:
+ *   a date d is a row when x_state[k][d][s] != ABSENT; period p is held when it has a row; the
+ *   signal of a held period is its last row's group and weight; prev(p) is the latest held
+ *   period before p (the stock's own, possibly earlier than p - 1: shift(1).over('code')).
+ *   m(p) = the group of prev(p)'s signal when p is held and prev(p) exists, else -1.
+ *   u(p) = 1.0 without a weight plane; with one, the weight of prev(p)'s signal when that is
+ *     VALUE, finite and > 0, else 0.0.  A member with u = 0 still counts as a member.  Stored
+ *     as 0.0 where m(p) = -1.
+ *   c(d), d in period p: 1.0 multiplied in date order by pct[d'] + 1.0 over the rows d' <= d of
+ *     p whose pct state is VALUE; cend(p) = c on the last date of p (1.0 when p is not held).
+ *   Bit for bit, m(p) is mff_bt_periods' p_group and cend(p) - 1.0 its p_ret.
+ * Per (k, p, g), over the stocks with m(p) = g:
+ *   n = their count, U = sum u; A(d) = sum u c(d) for every date d of p, A_end = A(last date).
+ *   V(d) = A(d) / U when U > 0, else 1.0 (cash); V before the first date of a period is 1.0.
+ *   ret[k][d][g] = V(d) / V(d-) - 1 (0 when U is not > 0); count[k][p][g] = n, the cell is
+ *   present when n > 0.  A NaN, infinite or -1 pct is not special-cased: IEEE arithmetic carries
+ *   it until the period ends.
+ * Turnover, p >= 1:
+ *   t_s = u_s(p) / U(p) when m_s(p) = g and U(p) > 0, else 0;
+ *   b_s = u_s(p-1) cend_s(p-1) / A_end(p-1) when m_s(p-1) = g and U(p-1) > 0, else 0;
+ *   traded[k][p][g] = sum_s |t_s - b_s|; traded[k][0][g] = 0.  Both sides of a trade count, in
+ *   units of portfolio value: built from cash = 1, a complete swap = 2.
+ *
+ * mff_pf_signal: m int8, u f64, cend f64, all [K][P][S_loc].
+ * mff_pf_sums: the daily pass over the local stocks -> a_partial f64 [K][D][G] = A and
+ *   nu_partial f64 [K][P][G][2] = (n, U).  One workgroup per (period, factor) walks the stocks
+ *   in tiles of 256; each stock-day is read once (x_state 1 byte per factor, pct and its state
+ *   once per tile) and added to the LDS bin of its group; no loop over the groups.
+ * mff_pf_finalize: sums the R shards' partials [R][K][D][G] and [R][K][P][G][2] in rank order
+ *   -> ret f64 [K][D][G], count int32 [K][P][G], tot f64 [K][P][G][2] = (U, A_end).
+ * mff_pf_traded: from the local m, u, cend and the merged tot -> partial f64 [K][P][G].
+ * mff_pf_traded_finalize: sums the R shards' partials [R][K][P][G] in rank order -> traded.
+ * Every output element is written.  No floating-point atomics: the summation order (stocks
+ * j, j + J, ... of a tile per bin, tiles in order, the J bins in order, ranks in order) depends on
+ * the shapes alone, so two runs are bit-identical.
+ * Errors (negative, nothing launched, nothing written): K < 1 or > 65535, a negative size, P
+ * outside [0, min(D, 65535)] or 0 with D > 0, G outside [1, 63], R < 1, weight without
+ * weight_state, a NULL buffer.  D == 0 or S == 0 is a success with nothing launched and nothing written (the partials
+ * of a shard without stocks are zeros the caller provides).
+ */
+int mff_pf_signal(const uint8_t* x_state, const int8_t* group, const double* pct,
+                  const uint8_t* pct_state, const double* weight, const uint8_t* weight_state,
+                  const int32_t* period_of, int K, int D, int S, int P, int8_t* m, double* u,
+                  double* cend, void* stream);
+int mff_pf_sums(const uint8_t* x_state, const double* pct, const uint8_t* pct_state,
+                const int32_t* period_of, const int8_t* m, const double* u, int K, int D, int S,
+                int P, int G, double* a_partial, double* nu_partial, void* stream);
+int mff_pf_finalize(const double* a_all, const double* nu_all, const int32_t* period_of, int R,
+                    int K, int D, int P, int G, double* ret, int32_t* count, double* tot,
+                    void* stream);
+int mff_pf_traded(const int8_t* m, const double* u, const double* cend, const double* tot, int K,
+                  int P, int S, int G, double* partial, void* stream);
+int mff_pf_traded_finalize(const double* partial_all, int R, int K, int P, int G, double* traded,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,12 +12,12 @@ from . import catalog  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["catalog", "combine", "factor_correlation", "factor_returns", "orthogonalize"]
+__all__ = ["catalog", "combine", "factor_correlation", "factor_returns", "orthogonalize", "portfolio_tests"]
 
 
 def __getattr__(name):
-    # mff.factor_correlation / mff.factor_returns / mff.orthogonalize / mff.combine, resolved on
-    # first use
+    # mff.factor_correlation / mff.factor_returns / mff.orthogonalize / mff.combine /
+    # mff.portfolio_tests, resolved on first use
     # (mff.factor pulls in pandas-side helpers)
     if name == "factor_correlation":
         from .factor import factor_correlation
@@ -31,4 +31,7 @@ def __getattr__(name):
     if name == "combine":
         from .factor import combine
         return combine
+    if name == "portfolio_tests":
+        from .factor import portfolio_tests
+        return portfolio_tests
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

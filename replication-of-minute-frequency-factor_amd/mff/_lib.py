@@ -87,6 +87,11 @@ SIGNATURES = {
     "mff_bt_periods": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "mff_bt_reduce": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
     "mff_bt_finalize": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    "mff_pf_signal": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "mff_pf_sums": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "mff_pf_finalize": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "mff_pf_traded": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "mff_pf_traded_finalize": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
 }
 
 _lock = threading.Lock()

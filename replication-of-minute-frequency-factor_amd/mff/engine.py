@@ -1512,6 +1512,99 @@ def group_returns(x_val: torch.Tensor, x_state: torch.Tensor, pct_val: torch.Ten
     return ret, present
 
 
+PORTFOLIO_MAX_GROUPS = 63  # G of mff_bt_qcut / mff_pf_*
+PORTFOLIO_BYTES = CORR_PLANE_BYTES  # cap of the exposure / group / signal planes of one factor chunk
+
+
+class PortfolioResult(NamedTuple):
+    """group_portfolios: the daily group portfolios of K factors (device tensors)."""
+    ret: torch.Tensor     # float64 [K][D][G]: daily return of each group's drifting-weight portfolio
+    count: torch.Tensor   # int32 [K][P][G]: members over all ranks; the cell is present when > 0
+    traded: torch.Tensor  # float64 [K][P][G]: two-sided turnover of the rebalance into period p
+
+
+def group_portfolios(x_val: torch.Tensor, x_state: torch.Tensor, pct_val: torch.Tensor,
+                     pct_state: torch.Tensor, period_of: torch.Tensor, P: int, group_num: int = 5,
+                     w_val: Optional[torch.Tensor] = None, w_state: Optional[torch.Tensor] = None,
+                     comm=None, stocks_total: Optional[int] = None) -> PortfolioResult:
+    """Daily simulation of the G quantile portfolios of the K exposure rows x [K][D][S_loc]
+    (mff_pf_*; the definition is on the declarations in include/mff.h): per factor the cut of
+    group_returns (mff_bt_qcut, unchanged), membership / weight / growth per stock and period
+    (mff_pf_signal), the daily value sums (mff_pf_sums), and the turnover of every rebalance
+    (mff_pf_traded).  pct and the optional weight are [D][S_loc], shared by the factors;
+    period_of: int32 [D] on the device.  Compounded over a period, ``ret`` is group_returns'
+    number for that period.
+
+    Stock-sharded (``comm``): the partial sums are all-gathered and merged in rank order."""
+    lib = _lib.load()
+    if x_val.dim() != 3 or x_state.shape != x_val.shape:
+        raise ValueError("x_val and x_state must be [K][D][S]")
+    K, D, S = x_val.shape
+    if K < 1:
+        raise ValueError("group_portfolios needs at least one factor")
+    G = _int_arg("group_num", group_num, 1)
+    if G > PORTFOLIO_MAX_GROUPS:
+        raise ValueError(f"group_num must be at most {PORTFOLIO_MAX_GROUPS}, got {group_num!r}")
+    P = _int_arg("P", P, 0)
+    if tuple(pct_val.shape) != (D, S) or pct_state.shape != pct_val.shape:
+        raise ValueError("pct_val and pct_state must be [D][S]")
+    if (w_val is None) != (w_state is None):
+        raise ValueError("w_val and w_state go together")
+    if w_val is not None and (tuple(w_val.shape) != (D, S) or w_state.shape != w_val.shape):
+        raise ValueError("w_val and w_state must be [D][S]")
+    if int(period_of.numel()) != D:
+        raise ValueError("period_of must hold one period per date")
+    dev = x_val.device
+    st = _stream(dev)
+    f64, u8, i8 = torch.float64, torch.uint8, torch.int8
+    R = 1 if comm is None else comm.world_size
+    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
+    pct_val, pct_state = pct_val.to(f64).contiguous(), pct_state.to(u8).contiguous()
+    period_of = period_of.to(torch.int32).contiguous()
+    if w_val is not None:
+        w_val, w_state = w_val.to(f64).contiguous(), w_state.to(u8).contiguous()
+    ret = torch.zeros((K, D, G), dtype=f64, device=dev)
+    count = torch.zeros((K, P, G), dtype=torch.int32, device=dev)
+    traded = torch.zeros((K, P, G), dtype=f64, device=dev)
+    if D == 0:
+        return PortfolioResult(ret, count, traded)
+    group = torch.full((K, D, S), -1, dtype=i8, device=dev)
+    if S > 0:
+        S_all = S if comm is None else shard_width(comm, S, stocks_total, dev)
+        ws = torch.empty(lib.mff_bt_qcut_workspace_bytes(D, S_all, R), dtype=u8, device=dev)
+        for k in range(K):
+            v_all = x_val[k] if comm is None else comm.all_gather(_pad_last(x_val[k], S_all, 0.0))
+            s_all = x_state[k] if comm is None else comm.all_gather(_pad_last(x_state[k], S_all, ABSENT))
+            _lib.check(lib.mff_bt_qcut(_lib.ptr(x_val[k]), _lib.ptr(x_state[k]), D, S, _lib.ptr(v_all),
+                                       _lib.ptr(s_all), R, S_all, G, _lib.ptr(group[k]), _lib.ptr(ws), st),
+                       "mff_bt_qcut")
+    m = torch.empty((K, P, S), dtype=i8, device=dev)
+    u = torch.empty((K, P, S), dtype=f64, device=dev)
+    cend = torch.empty((K, P, S), dtype=f64, device=dev)
+    _lib.check(lib.mff_pf_signal(_lib.ptr(x_state), _lib.ptr(group), _lib.ptr(pct_val), _lib.ptr(pct_state),
+                                 _lib.ptr(w_val), _lib.ptr(w_state), _lib.ptr(period_of), K, D, S, P,
+                                 _lib.ptr(m), _lib.ptr(u), _lib.ptr(cend), st), "mff_pf_signal")
+    del group
+    alloc = torch.zeros if S == 0 else torch.empty  # a shard without stocks: nothing is launched
+    a_part = alloc((K, D, G), dtype=f64, device=dev)
+    nu_part = alloc((K, P, G, 2), dtype=f64, device=dev)
+    _lib.check(lib.mff_pf_sums(_lib.ptr(x_state), _lib.ptr(pct_val), _lib.ptr(pct_state), _lib.ptr(period_of),
+                               _lib.ptr(m), _lib.ptr(u), K, D, S, P, G, _lib.ptr(a_part), _lib.ptr(nu_part), st),
+               "mff_pf_sums")
+    a_all = a_part if comm is None else comm.all_gather(a_part).contiguous()
+    nu_all = nu_part if comm is None else comm.all_gather(nu_part).contiguous()
+    tot = torch.empty((K, P, G, 2), dtype=f64, device=dev)
+    _lib.check(lib.mff_pf_finalize(_lib.ptr(a_all), _lib.ptr(nu_all), _lib.ptr(period_of), R, K, D, P, G,
+                                   _lib.ptr(ret), _lib.ptr(count), _lib.ptr(tot), st), "mff_pf_finalize")
+    t_part = alloc((K, P, G), dtype=f64, device=dev)
+    _lib.check(lib.mff_pf_traded(_lib.ptr(m), _lib.ptr(u), _lib.ptr(cend), _lib.ptr(tot), K, P, S, G,
+                                 _lib.ptr(t_part), st), "mff_pf_traded")
+    t_all = t_part if comm is None else comm.all_gather(t_part).contiguous()
+    _lib.check(lib.mff_pf_traded_finalize(_lib.ptr(t_all), R, K, P, G, _lib.ptr(traded), st),
+               "mff_pf_traded_finalize")
+    return PortfolioResult(ret, count, traded)
+
+
 def calendar(val: torch.Tensor, state: torch.Tensor, period_start: torch.Tensor, method: str):
     """MinFreqFactor.cal_final_exposure(mode='calendar') (MF:130-186, the build's definition):
     dense [D][S] -> [P][S] per calendar window (period_start int32 [P+1] on the device)."""

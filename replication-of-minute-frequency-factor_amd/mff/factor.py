@@ -15,6 +15,7 @@ Device work:
   cal_final_exposure(f, m, 'calendar') -> calendar resampling kernel
   ic_test                            -> future-return, IC pair / rank / moment kernels
   group_test                         -> qcut / period / reduce kernels
+  portfolio_test / portfolio_tests   -> qcut + daily portfolio kernels (mff_pf_*)
 coverage is a host group-by count.
 """
 from __future__ import annotations
@@ -231,6 +232,35 @@ class Factor:
                 plt.tight_layout()
                 plt.show()
         return group_df if return_df else None
+
+    def portfolio_test(self, frequency: Literal["weekly", "monthly", "quarterly", "yearly"] = "monthly",
+                       weight_param: Literal["tmc", "cmc", None] = None, group_num: int = 5, cost: float = 0.0,
+                       annual_days: int = 252, return_daily: bool = False, pv_data=None, device=None,
+                       plot_out: bool = True, return_df: bool = False):
+        """:func:`portfolio_tests` of this factor alone (arguments as there): the daily NAV of
+        the group_test portfolios and of group_G minus group_1, turnover and summary statistics
+        net of ``cost``.  The frames come without the ``factor`` column; ``plot_out`` draws the
+        NAV curves.  Returns None unless ``return_df``."""
+        out = portfolio_tests([self], frequency=frequency, weight_param=weight_param, group_num=group_num,
+                              cost=cost, annual_days=annual_days, return_daily=return_daily or plot_out,
+                              pv_data=pv_data, device=device)
+        summary, daily, periods = out if isinstance(out, tuple) else (out, None, None)
+        if plot_out:
+            plt = _plt()
+            if plt is not None:
+                plt.figure(figsize=(12, 8))
+                for pn, g in daily.groupby("portfolio", sort=False):
+                    plt.plot(g["date"], g["nav"], label=pn, linewidth=2)
+                plt.legend(loc="best")
+                plt.title("portfolio NAV", fontsize=16)
+                plt.tight_layout()
+                plt.show()
+        if not return_df:
+            return None
+        summary = summary.drop(columns="factor")
+        if not return_daily:
+            return summary
+        return summary, daily.drop(columns="factor"), periods.drop(columns="factor")
 
     def neutralize(self, industry=None, size: Literal["cmc", "tmc", None] = "cmc", winsor: float = 3.0,
                    standardize: bool = True, pv_data=None, device=None) -> "Factor":
@@ -706,6 +736,176 @@ def factor_correlation(factors, method: str = "pearson", min_pairs: int = 2, ret
                           "corr": corr[d_idx, iu[p_idx], ju[p_idx]],
                           "n": n[d_idx, iu[p_idx], ju[p_idx]]})
     return out, daily.sort_values(["date", "factor_a", "factor_b"], kind="stable").reset_index(drop=True)
+
+
+PORTFOLIO_SUMMARY = ("days", "total_return", "annual_return", "annual_vol", "sharpe", "max_drawdown",
+                     "mean_turnover", "total_cost")
+
+
+def _series_summary(ret_net, traded, present, cost, annual_days):
+    """Summary columns of one portfolio: ret_net [n] daily, traded / present [periods of the window]."""
+    n = len(ret_net)
+    nav = np.cumprod(1.0 + ret_net)
+    out = dict.fromkeys(PORTFOLIO_SUMMARY, np.nan)
+    out["days"] = n
+    out["total_cost"] = float(np.sum(cost * traded))
+    out["mean_turnover"] = float(np.mean(traded[present] / 2.0)) if present.any() else np.nan
+    if n == 0:
+        return out
+    out["total_return"] = float(nav[-1] - 1.0)
+    out["annual_return"] = float(nav[-1] ** (annual_days / n) - 1.0)
+    if n >= 2:
+        sd = float(np.std(ret_net, ddof=1))
+        out["annual_vol"] = sd * np.sqrt(annual_days)
+        if sd > 0:
+            out["sharpe"] = float(np.mean(ret_net)) / sd * np.sqrt(annual_days)
+    peak = np.maximum.accumulate(np.concatenate([[1.0], nav]))[1:]  # the running maximum starts at 1
+    out["max_drawdown"] = float(np.max(1.0 - nav / peak))
+    return out
+
+
+def portfolio_statistics(ret, count, traded, period_of, cost: float = 0.0, annual_days: int = 252):
+    """Host side of :func:`portfolio_tests` for one factor, numpy f64: ret [D][G], count [P][G],
+    traded [P][G] (engine.group_portfolios) -> a dict with
+
+    * ``names``: group_1..group_G and, when G >= 2, long_short (group_G minus group_1);
+    * ``d0`` / ``p0``: the window starts on the first date of the first period with a present
+      cell (count > 0) and runs to the last date; d0 = D, p0 = P when no cell is present;
+    * ``ret`` / ``ret_net`` / ``nav`` [names][D - d0]: ret_net = (1 + ret)(1 - cost traded(p)) - 1
+      on the first date of period p, else ret; long_short: ret_G - ret_1 less cost (traded_G +
+      traded_1) on a period's first date; nav = cumprod(1 + ret_net);
+    * ``traded`` [names][P - p0] (long_short: the sum of its legs), ``present`` likewise
+      (long_short: either leg);
+    * ``summary``: one dict of PORTFOLIO_SUMMARY per name: annual_return =
+      nav_last^(annual_days / days) - 1, annual_vol = std(ddof=1) sqrt(annual_days), sharpe =
+      mean / std sqrt(annual_days) (NaN when days < 2 or std = 0), max_drawdown against the
+      running maximum starting at 1, mean_turnover = mean of traded / 2 over the present
+      periods, total_cost = sum of cost traded."""
+    ret = np.asarray(ret, dtype=np.float64)
+    count, traded = np.asarray(count), np.asarray(traded, dtype=np.float64)
+    period_of = np.asarray(period_of, dtype=np.int64)
+    D, G = ret.shape
+    P = count.shape[0]
+    pres = count > 0
+    held = np.flatnonzero(pres.any(axis=1))
+    p0 = int(held[0]) if held.size else P
+    d0 = int(np.searchsorted(period_of, p0, side="left"))
+    per = period_of[d0:]
+    first = np.ones(D - d0, dtype=bool)
+    first[1:] = per[1:] != per[:-1]
+    names = [f"group_{g + 1}" for g in range(G)]
+    r = ret[d0:].T.copy()                                   # [G][n]
+    charge = np.where(first[None, :], cost * traded[per].T, 0.0)
+    rn = (1.0 + r) * (1.0 - charge) - 1.0
+    tr, pr = traded[p0:].T.copy(), pres[p0:].T.copy()
+    if G >= 2:
+        names.append("long_short")
+        ls = r[G - 1] - r[0]
+        r = np.vstack([r, ls])
+        rn = np.vstack([rn, ls - (charge[G - 1] + charge[0])])
+        tr = np.vstack([tr, tr[G - 1] + tr[0]])
+        pr = np.vstack([pr, pr[G - 1] | pr[0]])
+    nav = np.cumprod(1.0 + rn, axis=1)
+    summary = [_series_summary(rn[i], tr[i], pr[i], cost, annual_days) for i in range(len(names))]
+    return {"names": names, "d0": d0, "p0": p0, "ret": r, "ret_net": rn, "nav": nav, "traded": tr,
+            "present": pr, "summary": summary}
+
+
+def portfolio_tests(factors, frequency: Literal["weekly", "monthly", "quarterly", "yearly"] = "monthly",
+                    weight_param: Literal["tmc", "cmc", None] = None, group_num: int = 5, cost: float = 0.0,
+                    annual_days: int = 252, return_daily: bool = False, pv_data=None, device=None):
+    """Daily back-test of the ``group_num`` quantile portfolios of several factors at once on
+    the GPU (mff_pf_*, include/mff.h): the groups of :meth:`Factor.group_test`, held with
+    drifting weights between the rebalances of ``frequency``, give a daily return per group,
+    the top-minus-bottom portfolio and the turnover of every rebalance; the host turns them into
+    series net of ``cost`` (a rate in [0, 1) per unit traded, both sides counted) and summary
+    statistics (:func:`portfolio_statistics`).  Compounded over a period the daily return is
+    group_test's number.  No reference counterpart: Factor.py stops at one return per period.
+
+    ``factors``: a sequence of :class:`Factor` or a mapping name -> Factor (duplicate names
+    raise ValueError), aligned on the union of their codes and dates; ``pv_data`` (default: the
+    daily price-volume file) gives pct_change and the ``weight_param`` column.  Many factors run
+    through the device in chunks of at most engine.PORTFOLIO_BYTES of planes.
+
+    Returns a long frame [factor, portfolio, days, total_return, annual_return, annual_vol,
+    sharpe, max_drawdown, mean_turnover, total_cost] with portfolios group_1..group_G and (G >= 2)
+    long_short.  With ``return_daily=True`` also [date, factor, portfolio, ret, ret_net, nav] and
+    [date (period right edge), factor, group, count, turnover, cost] (turnover = traded / 2,
+    cost = ``cost`` x traded), both from the first period in which a group holds a stock."""
+    import torch
+
+    from . import engine
+    from .factors import _device
+
+    pd = _pd()
+    if weight_param not in (None, "tmc", "cmc"):
+        raise ValueError(f"weight_param must be 'tmc', 'cmc' or None, got {weight_param!r}")
+    G = engine._int_arg("group_num", group_num, 1)
+    if G > engine.PORTFOLIO_MAX_GROUPS:
+        raise ValueError(f"group_num must be at most {engine.PORTFOLIO_MAX_GROUPS}, got {group_num!r}")
+    annual_days = engine._int_arg("annual_days", annual_days, 1)
+    if isinstance(cost, bool) or not isinstance(cost, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(cost) < 1.0:
+        raise ValueError(f"cost must be a number in [0, 1), got {cost!r}")
+    cost = float(cost)
+    names, objs = _named_factors(factors, "portfolio_tests")
+    need = ["code", "date", "pct_change"] + ([weight_param] if weight_param else [])
+    pv = pv_data if pv_data is not None else Factor._read_daily_pv_data(need)
+    for c in need:
+        if c not in pv.columns:
+            raise ValueError(f"pv_data has no column {c!r}")
+    exposures = [f.factor_exposure for f in objs]
+    codes, dates = frames.universe(*exposures)
+    pv = pv[frames.rows_in(pv, codes, dates)]
+    period_of, labels = rebalance_periods(dates, frequency)
+    K, D, S, P = len(objs), len(dates), len(codes), len(labels)
+    dev = _device(device)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    pc_v, pc_s, _, _ = frames.from_long(pv, "pct_change", codes=codes, dates=dates)
+    pcv, pcs = t(pc_v), t(pc_s)
+    wv = ws = None
+    if weight_param is not None:
+        w_v, w_s, _, _ = frames.from_long(pv, weight_param, codes=codes, dates=dates)
+        wv, ws = t(w_v), t(w_s)
+    per_d = t(period_of.astype(np.int32))
+    kc = max(1, engine.PORTFOLIO_BYTES // max(1, D * S * 10 + P * S * 17))
+    ret = np.zeros((K, D, G))
+    count = np.zeros((K, P, G), dtype=np.int32)
+    traded = np.zeros((K, P, G))
+    for k0 in range(0, K, kc):
+        k1 = min(K, k0 + kc)
+        val = np.zeros((k1 - k0, D, S), dtype=np.float64)
+        state = np.zeros((k1 - k0, D, S), dtype=np.uint8)
+        for i in range(k0, k1):
+            val[i - k0], state[i - k0], _, _ = frames.from_long(exposures[i], objs[i].factor_name, codes=codes,
+                                                                 dates=dates)
+        res = engine.group_portfolios(t(val), t(state), pcv, pcs, per_d, P, G, wv, ws)
+        torch.cuda.synchronize(dev)
+        ret[k0:k1], count[k0:k1], traded[k0:k1] = (res.ret.cpu().numpy(), res.count.cpu().numpy(),
+                                                  res.traded.cpu().numpy())
+    dd, ll = np.asarray(dates, dtype=object), np.asarray(labels, dtype=object)
+    rows, daily, periods = [], [], []
+    for k, nm in enumerate(names):
+        st = portfolio_statistics(ret[k], count[k], traded[k], period_of, cost, annual_days)
+        for i, pn in enumerate(st["names"]):
+            rows.append({"factor": nm, "portfolio": pn, **st["summary"][i]})
+        if return_daily:
+            d0, p0 = st["d0"], st["p0"]
+            for i, pn in enumerate(st["names"]):
+                daily.append(pd.DataFrame({"date": dd[d0:], "factor": nm, "portfolio": pn, "ret": st["ret"][i],
+                                           "ret_net": st["ret_net"][i], "nav": st["nav"][i]}))
+            for g in range(G):
+                periods.append(pd.DataFrame({"date": ll[p0:], "factor": nm, "group": f"group_{g + 1}",
+                                             "count": count[k, p0:, g], "turnover": traded[k, p0:, g] / 2.0,
+                                             "cost": cost * traded[k, p0:, g]}))
+    out = pd.DataFrame(rows, columns=["factor", "portfolio", *PORTFOLIO_SUMMARY])
+    if not return_daily:
+        return out
+    daily_df = pd.concat(daily, ignore_index=True) if daily else pd.DataFrame(
+        columns=["date", "factor", "portfolio", "ret", "ret_net", "nav"])
+    period_df = pd.concat(periods, ignore_index=True) if periods else pd.DataFrame(
+        columns=["date", "factor", "group", "count", "turnover", "cost"])
+    return out, daily_df, period_df
 
 
 def rebalance_periods(dates, frequency: str):
