@@ -3,7 +3,7 @@
 // forward return in one pass over the K exposure rows, trailing-window weights per date from
 // the IC history, and the weighted sum of the per-date z-scores over the factors a stock has.
 //
-//   k_xc_moments   one workgroup per day, 512-stock chunks.  The chunk of y (values + states)
+//   k_comb_moments   one workgroup per day, 512-stock chunks.  The chunk of y (values + states)
 //                  is staged once in LDS for all K factors (Ky = 1); wave w takes the factors
 //                  w, w + 4, ...: eight stocks per lane in registers, so the chunk's moments are
 //                  the two passes of k_ic_moments / k_xs_moments without a second read (shift by
@@ -11,15 +11,15 @@
 //                  ballot popcounts), then the chunk is merged into the factor's running
 //                  (n, mean, M2 | n, mean_x, mean_y, Cxx, Cyy, Cxy) by the pairwise update, in
 //                  chunk order.  x and y are read once.
-//   k_xc_finalize  thread per (factor, day): the R shards' partials merged in rank order ->
+//   k_comb_finalize  thread per (factor, day): the R shards' partials merged in rank order ->
 //                  (n, mean, std), ic, n_pairs.
-//   k_xc_weights   one wave per date, lane = factor: the window's IC means / stds per lane in
+//   k_comb_weights   one wave per date, lane = factor: the window's IC means / stds per lane in
 //                  date order; max_icir: the listwise dates by ballot, the covariance rows in
 //                  registers (lane i owns row i; the date's deviations are broadcast through
-//                  LDS), unit-diagonal scaling, shrinkage of the off-diagonal, the unpivoted
-//                  Cholesky of k_xo_solve / k_xr_solve (row t on lane t) and the two triangular
-//                  solves column by column; sum |w| by the fixed-order wave sum.
-//   k_xc_apply     per (day, 1024-stock chunk): (w, mean, 1 / std) of the day's K factors in
+//                  LDS), unit-diagonal scaling, shrinkage of the off-diagonal, chol_lower
+//                  (mff_gram.h) and the two triangular solves column by column; sum |w| by the
+//                  fixed-order wave sum.
+//   k_comb_apply     per (day, 1024-stock chunk): (w, mean, 1 / std) of the day's K factors in
 //                  LDS, four stocks per thread, factors in row order; streaming: 9 B read per
 //                  (factor, stock-day), 9 B written per stock-day.
 // Every sum has one fixed order (lane tree of wsum, chunk order, rank order, date order, factor
@@ -27,24 +27,24 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mff.h"
+#include "mff_gram.h"
 #include "mff_internal.h"
 #include "mff_wave.h"
 
 namespace mff {
 
-constexpr int XC_MAX_K = 64;
-constexpr int XC_THREADS = 256;
-constexpr int XC_WAVES = XC_THREADS / WAVE;
-constexpr int XC_P = 8;                  // stocks per lane and chunk
-constexpr int XC_CHUNK = WAVE * XC_P;    // stocks per chunk of the moments pass (512)
-constexpr int XC_NP = 9;                 // entries of a partial
-constexpr int XC_LS = XC_MAX_K + 1;      // row stride of the weights kernel's matrix
-constexpr int XC_AP = 4;                 // stocks per thread of the apply pass
-constexpr int XC_AP_STOCKS = XC_THREADS * XC_AP;  // 1024
-constexpr double XC_PIV_MIN = 1e-10;     // the Cholesky pivot rule of k_xo_solve / k_xr_solve
+constexpr int COMB_MAX_K = 64;
+constexpr int COMB_THREADS = 256;
+constexpr int COMB_WAVES = COMB_THREADS / WAVE;
+constexpr int COMB_P = 8;                  // stocks per lane and chunk
+constexpr int COMB_CHUNK = WAVE * COMB_P;    // stocks per chunk of the moments pass (512)
+constexpr int COMB_NP = 9;                 // entries of a partial
+constexpr int COMB_AP = 4;                 // stocks per thread of the apply pass
+constexpr int COMB_AP_STOCKS = COMB_THREADS * COMB_AP;  // 1024
+static_assert(COMB_MAX_K <= GR_B, "k_comb_weights keeps its matrix with chol_lower's row stride");
 
 // b merged into a: (n, mean, M2)
-__device__ __forceinline__ void xc_merge3(double* a, double nb, double mb, double m2b) {
+__device__ __forceinline__ void comb_merge3(double* a, double nb, double mb, double m2b) {
   if (nb == 0.0) return;
   if (a[0] == 0.0) {
     a[0] = nb; a[1] = mb; a[2] = m2b;
@@ -56,7 +56,7 @@ __device__ __forceinline__ void xc_merge3(double* a, double nb, double mb, doubl
   a[0] = nt;
 }
 // b merged into a: (n, mean_x, mean_y, Cxx, Cyy, Cxy) (k_ic_finalize's update)
-__device__ __forceinline__ void xc_merge6(double* a, double nb, double mxb, double myb, double cxxb, double cyyb,
+__device__ __forceinline__ void comb_merge6(double* a, double nb, double mxb, double myb, double cxxb, double cyyb,
                                           double cxyb) {
   if (nb == 0.0) return;
   if (a[0] == 0.0) {
@@ -73,22 +73,23 @@ __device__ __forceinline__ void xc_merge6(double* a, double nb, double mxb, doub
 }
 
 // partial [K][D][9]; Ky: 0 = no y (the pair moments are 0), 1 = row 0 for every factor, K = row k
-__global__ __launch_bounds__(XC_THREADS) void k_xc_moments(const double* __restrict__ xv, const uint8_t* __restrict__ xs,
-                                                           int K, int D, int S, const double* __restrict__ yv,
-                                                           const uint8_t* __restrict__ ys, int Ky,
-                                                           double* __restrict__ part) {
-  __shared__ double ty[XC_CHUNK];
-  __shared__ uint8_t tys[XC_CHUNK];
-  __shared__ double acc[XC_MAX_K][XC_NP];
+__global__ __launch_bounds__(COMB_THREADS) void k_comb_moments(const double* __restrict__ xv,
+                                                               const uint8_t* __restrict__ xs, int K, int D, int S,
+                                                               const double* __restrict__ yv,
+                                                               const uint8_t* __restrict__ ys, int Ky,
+                                                               double* __restrict__ part) {
+  __shared__ double ty[COMB_CHUNK];
+  __shared__ uint8_t tys[COMB_CHUNK];
+  __shared__ double acc[COMB_MAX_K][COMB_NP];
   const int d = blockIdx.x, t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
   if (lane == 0)
-    for (int k = w; k < K; k += XC_WAVES)
+    for (int k = w; k < K; k += COMB_WAVES)
 #pragma unroll
-      for (int j = 0; j < XC_NP; ++j) acc[k][j] = 0.0;
-  for (int c0 = 0; c0 < S; c0 += XC_CHUNK) {
+      for (int j = 0; j < COMB_NP; ++j) acc[k][j] = 0.0;
+  for (int c0 = 0; c0 < S; c0 += COMB_CHUNK) {
     if (Ky == 1) {
       __syncthreads();  // the previous chunk's reads are done
-      for (int i = t; i < XC_CHUNK; i += XC_THREADS) {
+      for (int i = t; i < COMB_CHUNK; i += COMB_THREADS) {
         const int s = c0 + i;
         const bool in = s < S;
         ty[i] = in ? yv[(size_t)d * S + s] : 0.0;
@@ -96,12 +97,12 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_moments(const double* __restr
       }
       __syncthreads();
     }
-    for (int k = w; k < K; k += XC_WAVES) {
+    for (int k = w; k < K; k += COMB_WAVES) {
       const size_t row = ((size_t)k * D + d) * (size_t)S;
-      double x[XC_P], y[XC_P];
-      bool zin[XC_P], pin[XC_P];
+      double x[COMB_P], y[COMB_P];
+      bool zin[COMB_P], pin[COMB_P];
 #pragma unroll
-      for (int i = 0; i < XC_P; ++i) {
+      for (int i = 0; i < COMB_P; ++i) {
         const int s = c0 + i * WAVE + lane;
         const bool in = s < S;
         x[i] = in ? xv[row + s] : 0.0;
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_moments(const double* __restr
       int nz = 0, np = 0;
       double x0 = 0.0, px0 = 0.0, py0 = 0.0;
 #pragma unroll
-      for (int i = 0; i < XC_P; ++i) {
+      for (int i = 0; i < COMB_P; ++i) {
         const uint64_t bz = __ballot(zin[i]), bp = __ballot(pin[i]);
         if (bz && nz == 0) x0 = rdlane(x[i], __builtin_ctzll(bz));
         if (bp && np == 0) {
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_moments(const double* __restr
       if (nz == 0 && np == 0) continue;  // (wave-uniform)
       double s1 = 0.0, s1x = 0.0, s1y = 0.0;
 #pragma unroll
-      for (int i = 0; i < XC_P; ++i) {
+      for (int i = 0; i < COMB_P; ++i) {
         if (zin[i]) s1 += x[i] - x0;
         if (pin[i]) {
           s1x += x[i] - px0;
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_moments(const double* __restr
       const double mx = np ? px0 + s1x / (double)np : 0.0, my = np ? py0 + s1y / (double)np : 0.0;
       double m2 = 0.0, cxx = 0.0, cyy = 0.0, cxy = 0.0;
 #pragma unroll
-      for (int i = 0; i < XC_P; ++i) {
+      for (int i = 0; i < COMB_P; ++i) {
         if (zin[i]) {
           const double dl = x[i] - mz;
           m2 += dl * dl;
@@ -168,30 +169,31 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_moments(const double* __restr
       cyy = wsum(cyy);
       cxy = wsum(cxy);
       if (lane == 0) {  // (this wave alone touches acc[k])
-        xc_merge3(&acc[k][0], (double)nz, mz, m2);
-        xc_merge6(&acc[k][3], (double)np, mx, my, cxx, cyy, cxy);
+        comb_merge3(&acc[k][0], (double)nz, mz, m2);
+        comb_merge6(&acc[k][3], (double)np, mx, my, cxx, cyy, cxy);
       }
     }
   }
   if (lane == 0)
-    for (int k = w; k < K; k += XC_WAVES) {
-      double* p = part + ((size_t)k * D + d) * XC_NP;
+    for (int k = w; k < K; k += COMB_WAVES) {
+      double* p = part + ((size_t)k * D + d) * COMB_NP;
 #pragma unroll
-      for (int j = 0; j < XC_NP; ++j) p[j] = acc[k][j];
+      for (int j = 0; j < COMB_NP; ++j) p[j] = acc[k][j];
     }
 }
 
-__global__ __launch_bounds__(XC_THREADS) void k_xc_finalize(const double* __restrict__ parts, int R, int K, int D,
-                                                            int min_obs, double* __restrict__ zmom,
-                                                            double* __restrict__ ic, int32_t* __restrict__ npairs) {
+__global__ __launch_bounds__(COMB_THREADS) void k_comb_finalize(const double* __restrict__ parts, int R, int K, int D,
+                                                                int min_obs, double* __restrict__ zmom,
+                                                                double* __restrict__ ic,
+                                                                int32_t* __restrict__ npairs) {
   const size_t nseg = (size_t)K * D;
-  const size_t e = (size_t)blockIdx.x * XC_THREADS + threadIdx.x;
+  const size_t e = (size_t)blockIdx.x * COMB_THREADS + threadIdx.x;
   if (e >= nseg) return;
   double z[3] = {0.0, 0.0, 0.0}, c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int r = 0; r < R; ++r) {  // rank order
-    const double* p = parts + ((size_t)r * nseg + e) * XC_NP;
-    xc_merge3(z, p[0], p[1], p[2]);
-    xc_merge6(c, p[3], p[4], p[5], p[6], p[7], p[8]);
+    const double* p = parts + ((size_t)r * nseg + e) * COMB_NP;
+    comb_merge3(z, p[0], p[1], p[2]);
+    comb_merge6(c, p[3], p[4], p[5], p[6], p[7], p[8]);
   }
   zmom[e * 3 + 0] = z[0];
   zmom[e * 3 + 1] = z[1];
@@ -203,12 +205,12 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_finalize(const double* __rest
 }
 
 // one wave per date, lane = factor
-__global__ __launch_bounds__(WAVE) void k_xc_weights(const double* __restrict__ ic, int K, int D, int method, int h,
-                                                     int W, int m, double shrink, double* __restrict__ weights,
-                                                     int32_t* __restrict__ count, int32_t* __restrict__ status) {
-  __shared__ double A[XC_MAX_K * XC_LS];
-  __shared__ double bc[XC_MAX_K];  // a date's deviations / a solve's broadcast value
-  __shared__ double dg[XC_MAX_K];
+__global__ __launch_bounds__(WAVE) void k_comb_weights(const double* __restrict__ ic, int K, int D, int method, int h,
+                                                       int W, int m, double shrink, double* __restrict__ weights,
+                                                       int32_t* __restrict__ count, int32_t* __restrict__ status) {
+  __shared__ double A[COMB_MAX_K * GR_LS];
+  __shared__ double bc[COMB_MAX_K];  // a date's deviations / a solve's broadcast value
+  __shared__ double dg[COMB_MAX_K];
   const int d = blockIdx.x, k = threadIdx.x;
   const bool mine = k < K;
   const uint64_t full = ~0ull;
@@ -262,9 +264,9 @@ __global__ __launch_bounds__(WAVE) void k_xc_weights(const double* __restrict__ 
     if (cnt < need) stat = 1;
     if (stat == 0) {
       const double mu = v0 + s / (double)cnt;
-      double a[XC_MAX_K];
+      double a[COMB_MAX_K];
 #pragma unroll
-      for (int j = 0; j < XC_MAX_K; ++j) a[j] = 0.0;
+      for (int j = 0; j < COMB_MAX_K; ++j) a[j] = 0.0;
       for (long long e = lo; e <= hi; ++e) {  // lane i: row i of sum_L dev dev^T, date order
         const double v = mine ? row[e] : 0.0;
         if (__ballot(__builtin_isfinite(v)) != full) continue;
@@ -273,12 +275,12 @@ __global__ __launch_bounds__(WAVE) void k_xc_weights(const double* __restrict__ 
         bc[k] = dv;
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < XC_MAX_K; ++j) a[j] += dv * bc[j];
+        for (int j = 0; j < COMB_MAX_K; ++j) a[j] += dv * bc[j];
       }
 #pragma unroll
-      for (int j = 0; j < XC_MAX_K; ++j) A[k * XC_LS + j] = a[j];
+      for (int j = 0; j < COMB_MAX_K; ++j) A[k * GR_LS + j] = a[j];
       __syncthreads();
-      const double mkk = A[k * XC_LS + k];
+      const double mkk = A[k * GR_LS + k];
       dg[k] = mkk;
       if (__ballot(mine && !(mkk > 0.0)) != 0) stat = 2;  // a constant IC series (or not finite)
       __syncthreads();
@@ -286,48 +288,29 @@ __global__ __launch_bounds__(WAVE) void k_xc_weights(const double* __restrict__ 
         // unit diagonal, the off-diagonal shrunk: (1 - shrink) M_ij / sqrt(M_ii M_jj)
         if (mine)
           for (int j = 0; j < K; ++j)
-            A[k * XC_LS + j] = j == k ? 1.0 : (1.0 - shrink) * (A[k * XC_LS + j] / sqrt(mkk * dg[j]));
+            A[k * GR_LS + j] = j == k ? 1.0 : (1.0 - shrink) * (A[k * GR_LS + j] / sqrt(mkk * dg[j]));
         __syncthreads();
-        // unpivoted Cholesky, row t on lane t, L in the lower triangle (k_xo_solve)
-        for (int j = 0; j < K; ++j) {
-          const double piv = A[j * XC_LS + j];
-          if (!(piv > XC_PIV_MIN)) {  // (uniform: every lane reads the same entry)
-            stat = 2;
-            break;
-          }
-          const double ljj = sqrt(piv);
-          __syncthreads();
-          if (k == j) A[j * XC_LS + j] = ljj;
-          double lij = 0.0;
-          if (k > j && mine) {
-            lij = A[k * XC_LS + j] / ljj;
-            A[k * XC_LS + j] = lij;
-          }
-          __syncthreads();
-          if (k > j && mine)
-            for (int i = j + 1; i <= k; ++i) A[k * XC_LS + i] -= lij * A[i * XC_LS + j];
-          __syncthreads();
-        }
+        if (!chol_lower(A, K, k, CHOL_PIVOT_MIN)) stat = 2;  // row t on lane t
       }
       if (stat == 0) {
         const double sig = sqrt(mkk / (double)(cnt - 1));
         double b = mine ? mu / sig : 0.0;
         for (int j = 0; j < K; ++j) {  // L u = b, column by column
           if (k == j) {
-            b /= A[j * XC_LS + j];
+            b /= A[j * GR_LS + j];
             bc[j] = b;
           }
           __syncthreads();
-          if (k > j && mine) b -= A[k * XC_LS + j] * bc[j];
+          if (k > j && mine) b -= A[k * GR_LS + j] * bc[j];
           __syncthreads();
         }
         for (int j = K - 1; j >= 0; --j) {  // L^T v = u
           if (k == j) {
-            b /= A[j * XC_LS + j];
+            b /= A[j * GR_LS + j];
             bc[j] = b;
           }
           __syncthreads();
-          if (k < j) b -= A[j * XC_LS + k] * bc[j];
+          if (k < j) b -= A[j * GR_LS + k] * bc[j];
           __syncthreads();
         }
         wraw = mine ? b / sig : 0.0;
@@ -343,14 +326,15 @@ __global__ __launch_bounds__(WAVE) void k_xc_weights(const double* __restrict__ 
   if (k == 0) status[d] = stat;
 }
 
-__global__ __launch_bounds__(XC_THREADS) void k_xc_apply(const double* __restrict__ xv, const uint8_t* __restrict__ xs,
-                                                         int K, int D, int S, const double* __restrict__ zmom,
-                                                         const double* __restrict__ weights,
-                                                         const int32_t* __restrict__ status, int min_factors,
-                                                         double* __restrict__ ov, uint8_t* __restrict__ os) {
-  __shared__ double sw[XC_MAX_K], sm[XC_MAX_K], si[XC_MAX_K];
+__global__ __launch_bounds__(COMB_THREADS) void k_comb_apply(const double* __restrict__ xv,
+                                                             const uint8_t* __restrict__ xs, int K, int D, int S,
+                                                             const double* __restrict__ zmom,
+                                                             const double* __restrict__ weights,
+                                                             const int32_t* __restrict__ status, int min_factors,
+                                                             double* __restrict__ ov, uint8_t* __restrict__ os) {
+  __shared__ double sw[COMB_MAX_K], sm[COMB_MAX_K], si[COMB_MAX_K];
   const int d = blockIdx.x, t = threadIdx.x;
-  const int s0 = blockIdx.y * XC_AP_STOCKS + t;
+  const int s0 = blockIdx.y * COMB_AP_STOCKS + t;
   const bool ok = status[d] == 0;
   if (t < K) {
     const double* z = zmom + ((size_t)t * D + d) * 3;
@@ -361,11 +345,11 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_apply(const double* __restric
     si[t] = use ? 1.0 / sd : 0.0;
   }
   __syncthreads();
-  double num[XC_AP], den[XC_AP];
-  int cnt[XC_AP];
-  bool any[XC_AP];
+  double num[COMB_AP], den[COMB_AP];
+  int cnt[COMB_AP];
+  bool any[COMB_AP];
 #pragma unroll
-  for (int i = 0; i < XC_AP; ++i) {
+  for (int i = 0; i < COMB_AP; ++i) {
     num[i] = den[i] = 0.0;
     cnt[i] = 0;
     any[i] = false;
@@ -373,16 +357,16 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_apply(const double* __restric
   for (int k = 0; k < K; ++k) {  // factor order
     const size_t row = ((size_t)k * D + d) * (size_t)S;
     const double wk = sw[k], mean = sm[k], istd = si[k];
-    uint8_t st[XC_AP];
-    double x[XC_AP];
+    uint8_t st[COMB_AP];
+    double x[COMB_AP];
 #pragma unroll
-    for (int i = 0; i < XC_AP; ++i) {
-      const int s = s0 + i * XC_THREADS;
+    for (int i = 0; i < COMB_AP; ++i) {
+      const int s = s0 + i * COMB_THREADS;
       st[i] = s < S ? xs[row + s] : (uint8_t)MFF_STATE_ABSENT;
       x[i] = (ok && s < S) ? xv[row + s] : 0.0;
     }
 #pragma unroll
-    for (int i = 0; i < XC_AP; ++i) {
+    for (int i = 0; i < COMB_AP; ++i) {
       any[i] = any[i] || st[i] != MFF_STATE_ABSENT;
       if (wk != 0.0 && st[i] == MFF_STATE_VALUE && __builtin_isfinite(x[i])) {
         num[i] += wk * ((x[i] - mean) * istd);
@@ -392,8 +376,8 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_apply(const double* __restric
     }
   }
 #pragma unroll
-  for (int i = 0; i < XC_AP; ++i) {
-    const int s = s0 + i * XC_THREADS;
+  for (int i = 0; i < COMB_AP; ++i) {
+    const int s = s0 + i * COMB_THREADS;
     if (s >= S) continue;
     const bool val = ok && cnt[i] >= min_factors;
     ov[(size_t)d * S + s] = val ? num[i] / den[i] : 0.0;
@@ -401,12 +385,7 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_apply(const double* __restric
   }
 }
 
-static int xc_check(const char* what, int K, int D, int S) {
-  MFF_REQUIRE(K >= 1 && K <= XC_MAX_K, "%s: K=%d outside [1, %d]", what, K, XC_MAX_K);
-  MFF_REQUIRE(D >= 0 && S >= 0, "%s: bad sizes D=%d S=%d", what, D, S);
-  MFF_REQUIRE(S < (1 << 24) && (long long)D * S < (1ll << 40), "%s: panel too large", what);
-  return 0;
-}
+static int comb_check(const char* what, int K, int D, int S) { return xs_check(what, K, COMB_MAX_K, D, S); }
 
 }  // namespace mff
 
@@ -417,14 +396,14 @@ extern "C" {
 int mff_xs_comb_moments(const double* x_val, const uint8_t* x_state, int K, int D, int S, const double* y_val,
                         const uint8_t* y_state, int Ky, double* partial, void* stream) {
   clear_error();
-  if (int rc = xc_check("mff_xs_comb_moments", K, D, S)) return rc;
+  if (int rc = comb_check("mff_xs_comb_moments", K, D, S)) return rc;
   MFF_REQUIRE(Ky == 0 || Ky == 1 || Ky == K, "mff_xs_comb_moments: Ky=%d is not 0, 1 or K=%d", Ky, K);
   if (D == 0) return 0;
   // (an empty stock axis has no buffers to speak of)
   MFF_REQUIRE(S == 0 || ((Ky == 0) == (y_val == nullptr) && (y_val == nullptr) == (y_state == nullptr)),
               "mff_xs_comb_moments: Ky=%d does not match y_val / y_state (Ky = 0 means no y)", Ky);
   MFF_REQUIRE(partial && (S == 0 || (x_val && x_state)), "mff_xs_comb_moments: NULL buffer");
-  hipLaunchKernelGGL(k_xc_moments, dim3((unsigned)D), dim3(XC_THREADS), 0, as_stream(stream), x_val, x_state, K, D,
+  hipLaunchKernelGGL(k_comb_moments, dim3((unsigned)D), dim3(COMB_THREADS), 0, as_stream(stream), x_val, x_state, K, D,
                      S, y_val, y_state, Ky, partial);
   MFF_LAUNCH_CHECK();
   return 0;
@@ -433,13 +412,13 @@ int mff_xs_comb_moments(const double* x_val, const uint8_t* x_state, int K, int 
 int mff_xs_comb_finalize(const double* partial_all, int R, int K, int D, int min_obs, double* zmom, double* ic,
                          int32_t* n_pairs, void* stream) {
   clear_error();
-  if (int rc = xc_check("mff_xs_comb_finalize", K, D, 0)) return rc;
+  if (int rc = comb_check("mff_xs_comb_finalize", K, D, 0)) return rc;
   MFF_REQUIRE(R >= 1, "mff_xs_comb_finalize: R=%d shards", R);
   MFF_REQUIRE(min_obs >= 0, "mff_xs_comb_finalize: min_obs=%d below 0", min_obs);
   if (D == 0) return 0;
   MFF_REQUIRE(partial_all && zmom && ic && n_pairs, "mff_xs_comb_finalize: NULL buffer");
   const size_t nseg = (size_t)K * D;
-  hipLaunchKernelGGL(k_xc_finalize, dim3((unsigned)((nseg + XC_THREADS - 1) / XC_THREADS)), dim3(XC_THREADS), 0,
+  hipLaunchKernelGGL(k_comb_finalize, dim3((unsigned)((nseg + COMB_THREADS - 1) / COMB_THREADS)), dim3(COMB_THREADS), 0,
                      as_stream(stream), partial_all, R, K, D, min_obs, zmom, ic, n_pairs);
   MFF_LAUNCH_CHECK();
   return 0;
@@ -448,7 +427,7 @@ int mff_xs_comb_finalize(const double* partial_all, int R, int K, int D, int min
 int mff_xs_comb_weights(const double* ic, int K, int D, int method, int future_days, int window, int min_periods,
                         double shrink, double* weights, int32_t* count, int32_t* status, void* stream) {
   clear_error();
-  if (int rc = xc_check("mff_xs_comb_weights", K, D, 0)) return rc;
+  if (int rc = comb_check("mff_xs_comb_weights", K, D, 0)) return rc;
   MFF_REQUIRE(method >= 0 && method <= 3, "mff_xs_comb_weights: method=%d (0 equal, 1 ic, 2 icir, 3 max_icir)",
               method);
   MFF_REQUIRE(future_days >= 1, "mff_xs_comb_weights: future_days=%d below 1", future_days);
@@ -457,7 +436,7 @@ int mff_xs_comb_weights(const double* ic, int K, int D, int method, int future_d
   MFF_REQUIRE(shrink >= 0.0 && shrink <= 1.0, "mff_xs_comb_weights: shrink=%g outside [0, 1]", shrink);
   if (D == 0) return 0;
   MFF_REQUIRE(weights && count && status && (ic || method == 0), "mff_xs_comb_weights: NULL buffer");
-  hipLaunchKernelGGL(k_xc_weights, dim3((unsigned)D), dim3(WAVE), 0, as_stream(stream), ic, K, D, method,
+  hipLaunchKernelGGL(k_comb_weights, dim3((unsigned)D), dim3(WAVE), 0, as_stream(stream), ic, K, D, method,
                      future_days, window, min_periods, shrink, weights, count, status);
   MFF_LAUNCH_CHECK();
   return 0;
@@ -467,13 +446,13 @@ int mff_xs_comb_apply(const double* x_val, const uint8_t* x_state, int K, int D,
                       const double* weights, const int32_t* status, int min_factors, double* out_val,
                       uint8_t* out_state, void* stream) {
   clear_error();
-  if (int rc = xc_check("mff_xs_comb_apply", K, D, S)) return rc;
+  if (int rc = comb_check("mff_xs_comb_apply", K, D, S)) return rc;
   MFF_REQUIRE(min_factors >= 1 && min_factors <= K, "mff_xs_comb_apply: min_factors=%d outside [1, K=%d]",
               min_factors, K);
   if (D == 0 || S == 0) return 0;
   MFF_REQUIRE(x_val && x_state && zmom && weights && status && out_val && out_state, "mff_xs_comb_apply: NULL buffer");
-  hipLaunchKernelGGL(k_xc_apply, dim3((unsigned)D, (unsigned)((S + XC_AP_STOCKS - 1) / XC_AP_STOCKS)),
-                     dim3(XC_THREADS), 0, as_stream(stream), x_val, x_state, K, D, S, zmom, weights, status,
+  hipLaunchKernelGGL(k_comb_apply, dim3((unsigned)D, (unsigned)((S + COMB_AP_STOCKS - 1) / COMB_AP_STOCKS)),
+                     dim3(COMB_THREADS), 0, as_stream(stream), x_val, x_state, K, D, S, zmom, weights, status,
                      min_factors, out_val, out_state);
   MFF_LAUNCH_CHECK();
   return 0;

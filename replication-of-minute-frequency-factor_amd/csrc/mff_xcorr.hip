@@ -10,10 +10,10 @@
 // at most S terms, so it is exact in f64.
 //
 // k_xc_sums_diag / k_xc_sums_off: one 256-thread workgroup per (day, 64-row block I, 64-row
-// block J).  A tile of XC_KT stocks of a block's rows goes through LDS as ONE f64 plane:
+// block J).  A tile of GR_KT stocks of a block's rows goes through LDS as ONE f64 plane:
 // y = x - centre where the entry is usable, NaN where it is not, so y, y^2 and the mask are
 // derived in registers from one ds_read_b64 per operand.  The tile is row-major with a row
-// stride of XC_KT + 2 doubles (68 dwords = 4 mod 64): the 32 lanes of one ds_read_b64 group
+// stride of GR_KT + 2 doubles (68 dwords = 4 mod 64): the 32 lanes of one ds_read_b64 group
 // (16 rows x 2 stocks) hit 32 distinct even banks, and the stores (32 consecutive stocks of
 // a row) are conflict-free too.  The next tile's values and states are loaded into registers
 // before the MFMAs of the current one.  Tile assignment: on the two kernels below.
@@ -22,23 +22,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mff.h"
+#include "mff_gram.h"
 #include "mff_internal.h"
 #include "mff_wave.h"
 
 namespace mff {
 
-constexpr int XC_B = 64;            // rows per block
-constexpr int XC_KT = 32;           // stocks per LDS tile
-constexpr int XC_STR = XC_KT + 2;   // row stride of the tile (doubles)
-constexpr int XC_THREADS = 256;
 constexpr int XC_MAX_ROWS = 1024;
 constexpr double XC_CONST_REL = 1e-12;  // the constant rule: var <= XC_CONST_REL * Q
-
-typedef double xc_v4d __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool xc_usable(double x, uint8_t s) {
-  return s == MFF_STATE_VALUE && __builtin_isfinite(x);
-}
 
 // per (row, day): n and sum of x over the usable set -> [rows][D][2]; one wave per segment
 __global__ __launch_bounds__(256) void k_xc_moments(const double* __restrict__ val, const uint8_t* __restrict__ state,
@@ -53,7 +44,7 @@ __global__ __launch_bounds__(256) void k_xc_moments(const double* __restrict__ v
 #pragma unroll 4
   for (int s = l; s < S; s += WAVE) {
     const double x = v[s];
-    const bool u = xc_usable(x, st[s]);
+    const bool u = xs_usable(x, st[s]);
     sum += u ? x : 0.0;
     n += u ? 1u : 0u;
   }
@@ -75,7 +66,7 @@ __global__ __launch_bounds__(256) void k_xc_center(const double* __restrict__ mo
 }
 
 struct XcAcc {
-  xc_v4d A[4], Q[4], P[4], N[4];
+  v4d A[4], Q[4], P[4], N[4];
 };
 
 template <bool SYM>
@@ -83,14 +74,14 @@ __device__ __forceinline__ void xc_tile_mma(const double* __restrict__ ti, const
                                             XcAcc& acc) {
   const int r = l & 15, kq = l >> 4;
 #pragma unroll
-  for (int ks = 0; ks < XC_KT / 4; ++ks) {
+  for (int ks = 0; ks < GR_KT / 4; ++ks) {
     const int k = ks * 4 + kq;
-    const double a = ti[(16 * w + r) * XC_STR + k];
+    const double a = ti[(16 * w + r) * GR_STR + k];
     const bool ua = a == a;
     const double ya = ua ? a : 0.0, fa = ua ? 1.0 : 0.0, qa = ya * ya;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const double b = tj[(16 * c + r) * XC_STR + k];
+      const double b = tj[(16 * c + r) * GR_STR + k];
       const bool ub = b == b;
       const double yb = ub ? b : 0.0, fb = ub ? 1.0 : 0.0;
       acc.A[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya, fb, acc.A[c], 0, 0, 0);
@@ -103,17 +94,14 @@ __device__ __forceinline__ void xc_tile_mma(const double* __restrict__ ti, const
   }
 }
 
-// this thread's part of a [64 rows][XC_KT stocks] tile: stock t % XC_KT, rows t / XC_KT + 8 i
-constexpr int XC_NR = XC_B * XC_KT / XC_THREADS;  // rows per thread (8)
-constexpr int XC_RS = XC_THREADS / XC_KT;         // row step (8)
-
+// this thread's part of a [64 rows][GR_KT stocks] tile: stock t % GR_KT, rows t / GR_KT + 8 i
 __device__ __forceinline__ void xc_load(const double* __restrict__ val, const uint8_t* __restrict__ state, int rows,
-                                        int D, int S, int d, int row0, int k0, double (&xv)[XC_NR],
-                                        uint8_t (&xs)[XC_NR]) {
-  const int s = k0 + (int)(threadIdx.x & (XC_KT - 1));
+                                        int D, int S, int d, int row0, int k0, double (&xv)[GR_NR],
+                                        uint8_t (&xs)[GR_NR]) {
+  const int s = k0 + (int)(threadIdx.x & (GR_KT - 1));
 #pragma unroll
-  for (int i = 0; i < XC_NR; ++i) {
-    const int g = row0 + (int)(threadIdx.x / XC_KT) + XC_RS * i;
+  for (int i = 0; i < GR_NR; ++i) {
+    const int g = row0 + (int)(threadIdx.x / GR_KT) + GR_RS * i;
     const bool ok = g < rows && s < S;
     const size_t off = ((size_t)g * D + d) * (size_t)S + s;
     xv[i] = ok ? val[off] : 0.0;
@@ -122,12 +110,12 @@ __device__ __forceinline__ void xc_load(const double* __restrict__ val, const ui
 }
 // y = x - centre where usable, NaN where not (a padding row's centre is NaN)
 __device__ __forceinline__ void xc_store(double* __restrict__ tile, const double* __restrict__ cen,
-                                         const double (&xv)[XC_NR], const uint8_t (&xs)[XC_NR]) {
-  const int ls = threadIdx.x & (XC_KT - 1);
+                                         const double (&xv)[GR_NR], const uint8_t (&xs)[GR_NR]) {
+  const int ls = threadIdx.x & (GR_KT - 1);
 #pragma unroll
-  for (int i = 0; i < XC_NR; ++i) {
-    const int r = (int)(threadIdx.x / XC_KT) + XC_RS * i;
-    tile[r * XC_STR + ls] = xc_usable(xv[i], xs[i]) ? xv[i] - cen[r] : qnan();
+  for (int i = 0; i < GR_NR; ++i) {
+    const int r = (int)(threadIdx.x / GR_KT) + GR_RS * i;
+    tile[r * GR_STR + ls] = xs_usable(xv[i], xs[i]) ? xv[i] - cen[r] : qnan();
   }
 }
 
@@ -136,42 +124,42 @@ __device__ __forceinline__ void xc_store(double* __restrict__ tile, const double
 // need only the 10 tiles on or below the diagonal each, and those 20 are split 5 per wave:
 // waves 0 / 1 take P, waves 2 / 3 take n, of tile rows {0, 3} (1 + 4 tiles) and {1, 2}
 // (2 + 3 tiles).  13 accumulator tiles per wave instead of 16, and two workgroups per CU.
-__global__ __launch_bounds__(XC_THREADS, 2) void k_xc_sums_diag(const double* __restrict__ val,
+__global__ __launch_bounds__(GR_THREADS, 2) void k_xc_sums_diag(const double* __restrict__ val,
                                                                 const uint8_t* __restrict__ state, int rows, int D,
                                                                 int S, const double* __restrict__ center,
                                                                 double* __restrict__ sums) {
-  __shared__ double tI[XC_B * XC_STR];
-  __shared__ double cen[XC_B];
+  __shared__ double tI[GR_B * GR_STR];
+  __shared__ double cen[GR_B];
   const int d = blockIdx.x, bi = blockIdx.y;
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  if (t < XC_B) {
-    const int g = bi * XC_B + t;
+  if (t < GR_B) {
+    const int g = bi * GR_B + t;
     cen[t] = g < rows ? center[(size_t)g * D + d] : qnan();
   }
-  double xv[XC_NR];
-  uint8_t xs[XC_NR];
-  xc_v4d A[4], Q[4], T[5];
+  double xv[GR_NR];
+  uint8_t xs[GR_NR];
+  v4d A[4], Q[4], T[5];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) A[c] = Q[c] = xc_v4d{0.0, 0.0, 0.0, 0.0};
+  for (int c = 0; c < 4; ++c) A[c] = Q[c] = v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int k = 0; k < 5; ++k) T[k] = xc_v4d{0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < 5; ++k) T[k] = v4d{0.0, 0.0, 0.0, 0.0};
   const bool g1 = (w & 1) != 0;  // tile rows {1, 2}, else {0, 3}
   const bool cnt = w >= 2;       // the n plane, else P
   const int r = l & 15, kq = l >> 4;
 
-  if (S > 0) xc_load(val, state, rows, D, S, d, bi * XC_B, 0, xv, xs);
-  for (int k0 = 0; k0 < S; k0 += XC_KT) {
+  if (S > 0) xc_load(val, state, rows, D, S, d, bi * GR_B, 0, xv, xs);
+  for (int k0 = 0; k0 < S; k0 += GR_KT) {
     __syncthreads();  // the previous tile's reads are done (first pass: cen is written)
     xc_store(tI, cen, xv, xs);
     __syncthreads();
-    if (k0 + XC_KT < S) xc_load(val, state, rows, D, S, d, bi * XC_B, k0 + XC_KT, xv, xs);
+    if (k0 + GR_KT < S) xc_load(val, state, rows, D, S, d, bi * GR_B, k0 + GR_KT, xv, xs);
 #pragma unroll
-    for (int ks = 0; ks < XC_KT / 4; ++ks) {
+    for (int ks = 0; ks < GR_KT / 4; ++ks) {
       const int k = ks * 4 + kq;
       double y[4], f[4], z[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const double b = tI[(16 * c + r) * XC_STR + k];
+        const double b = tI[(16 * c + r) * GR_STR + k];
         const bool u = b == b;
         y[c] = u ? b : 0.0;
         f[c] = u ? 1.0 : 0.0;
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(XC_THREADS, 2) void k_xc_sums_diag(const double* __
 
   const size_t plane = (size_t)rows * rows;
   double* out = sums + (size_t)d * 4 * plane;
-  const int base = bi * XC_B;
+  const int base = bi * GR_B;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int j = base + 16 * c + r;
@@ -227,41 +215,41 @@ __global__ __launch_bounds__(XC_THREADS, 2) void k_xc_sums_diag(const double* __
 // Off-diagonal blocks (I != J): wave w owns tile row w of block I against the four tile
 // columns of block J for every product, 16 accumulator tiles, one wave per SIMD.  J < I: all
 // four planes, P and n written mirrored too; J > I: A and Q only.
-__global__ __launch_bounds__(XC_THREADS) void k_xc_sums_off(const double* __restrict__ val,
+__global__ __launch_bounds__(GR_THREADS) void k_xc_sums_off(const double* __restrict__ val,
                                                             const uint8_t* __restrict__ state, int rows, int D, int S,
                                                             const double* __restrict__ center,
                                                             double* __restrict__ sums) {
-  __shared__ double tI[XC_B * XC_STR];
-  __shared__ double tJ[XC_B * XC_STR];
-  __shared__ double cen[2][XC_B];
+  __shared__ double tI[GR_B * GR_STR];
+  __shared__ double tJ[GR_B * GR_STR];
+  __shared__ double cen[2][GR_B];
   const int d = blockIdx.x;
-  const int nb = (rows + XC_B - 1) / XC_B;
+  const int nb = (rows + GR_B - 1) / GR_B;
   const int bi = (int)blockIdx.y / (nb - 1), rj = (int)blockIdx.y % (nb - 1), bj = rj + (rj >= bi ? 1 : 0);
   const bool sym = bj < bi;
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
 
-  if (t < 2 * XC_B) {
-    const int g = (t < XC_B ? bi : bj) * XC_B + (t & (XC_B - 1));
-    cen[t / XC_B][t & (XC_B - 1)] = g < rows ? center[(size_t)g * D + d] : qnan();
+  if (t < 2 * GR_B) {
+    const int g = (t < GR_B ? bi : bj) * GR_B + (t & (GR_B - 1));
+    cen[t / GR_B][t & (GR_B - 1)] = g < rows ? center[(size_t)g * D + d] : qnan();
   }
-  double xvI[XC_NR], xvJ[XC_NR];
-  uint8_t xsI[XC_NR], xsJ[XC_NR];
+  double xvI[GR_NR], xvJ[GR_NR];
+  uint8_t xsI[GR_NR], xsJ[GR_NR];
   XcAcc acc;
 #pragma unroll
-  for (int c = 0; c < 4; ++c) acc.A[c] = acc.Q[c] = acc.P[c] = acc.N[c] = xc_v4d{0.0, 0.0, 0.0, 0.0};
+  for (int c = 0; c < 4; ++c) acc.A[c] = acc.Q[c] = acc.P[c] = acc.N[c] = v4d{0.0, 0.0, 0.0, 0.0};
 
   if (S > 0) {
-    xc_load(val, state, rows, D, S, d, bi * XC_B, 0, xvI, xsI);
-    xc_load(val, state, rows, D, S, d, bj * XC_B, 0, xvJ, xsJ);
+    xc_load(val, state, rows, D, S, d, bi * GR_B, 0, xvI, xsI);
+    xc_load(val, state, rows, D, S, d, bj * GR_B, 0, xvJ, xsJ);
   }
-  for (int k0 = 0; k0 < S; k0 += XC_KT) {
+  for (int k0 = 0; k0 < S; k0 += GR_KT) {
     __syncthreads();  // the previous tile's reads are done (first pass: cen is written)
     xc_store(tI, cen[0], xvI, xsI);
     xc_store(tJ, cen[1], xvJ, xsJ);
     __syncthreads();
-    if (k0 + XC_KT < S) {
-      xc_load(val, state, rows, D, S, d, bi * XC_B, k0 + XC_KT, xvI, xsI);
-      xc_load(val, state, rows, D, S, d, bj * XC_B, k0 + XC_KT, xvJ, xsJ);
+    if (k0 + GR_KT < S) {
+      xc_load(val, state, rows, D, S, d, bi * GR_B, k0 + GR_KT, xvI, xsI);
+      xc_load(val, state, rows, D, S, d, bj * GR_B, k0 + GR_KT, xvJ, xsJ);
     }
     if (sym)
       xc_tile_mma<true>(tI, tJ, w, l, acc);
@@ -273,10 +261,10 @@ __global__ __launch_bounds__(XC_THREADS) void k_xc_sums_off(const double* __rest
   double* out = sums + (size_t)d * 4 * plane;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const int j = bj * XC_B + 16 * c + (l & 15);
+    const int j = bj * GR_B + 16 * c + (l & 15);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int i = bi * XC_B + 16 * w + (l >> 4) + 4 * q;
+      const int i = bi * GR_B + 16 * w + (l >> 4) + 4 * q;
       if (i >= rows || j >= rows) continue;
       const size_t ij = (size_t)i * rows + j, ji = (size_t)j * rows + i;
       out[plane + ij] = acc.A[c][q];
@@ -404,12 +392,12 @@ int mff_xs_corr_sums(const double* val, const uint8_t* state, int rows, int D, i
     MFF_LAUNCH_CHECK();
     center = cen;
   }
-  const int nb = (rows + XC_B - 1) / XC_B;
-  hipLaunchKernelGGL(k_xc_sums_diag, dim3((unsigned)D, (unsigned)nb), dim3(XC_THREADS), 0, st, val, state, rows, D, S,
+  const int nb = (rows + GR_B - 1) / GR_B;
+  hipLaunchKernelGGL(k_xc_sums_diag, dim3((unsigned)D, (unsigned)nb), dim3(GR_THREADS), 0, st, val, state, rows, D, S,
                      center, sums);
   MFF_LAUNCH_CHECK();
   if (nb > 1) {
-    hipLaunchKernelGGL(k_xc_sums_off, dim3((unsigned)D, (unsigned)(nb * (nb - 1))), dim3(XC_THREADS), 0, st, val, state,
+    hipLaunchKernelGGL(k_xc_sums_off, dim3((unsigned)D, (unsigned)(nb * (nb - 1))), dim3(GR_THREADS), 0, st, val, state,
                        rows, D, S, center, sums);
     MFF_LAUNCH_CHECK();
   }

@@ -16,23 +16,16 @@
 //                per-day scalars (n, non-empty industries, the between-industry part of the
 //                r2 denominator, the raw second moments).
 //   k_xr_gram    one workgroup per (day, stock split): sum w c~ c~^T of the C = K + 1 columns
-//                on v_mfma_f64_16x16x4_f64.  A 32-stock tile of c~ (0 outside U) goes through
-//                LDS as one plane with mff_xcorr.hip's row stride of 34 doubles (DESIGN.md §10:
-//                conflict-free ds_read_b64 and stores), the tile's weights as 32 doubles next to
-//                it; the second operand w c~ is one multiply in registers.  The next tile's
-//                values are in registers before the MFMAs of the current one.  The four waves
-//                split the k steps of a tile (stocks 8 w .. 8 w + 7), each holds the 10 tiles
-//                on or below the block diagonal (tile rows above ceil(C / 16) are skipped), and
-//                the four partial sums are added in wave order through LDS, then mirrored.
+//                (c~ is 0 outside U): gram_block (mff_gram.h) with the weight operand.
 //   k_xr_solve   one wave per day: the planes of the shards / splits added in plane order, the
-//                singular rule, unit-diagonal scaling, unpivoted Cholesky in LDS, the two
-//                triangular solves and diag(M^-1) from the columns of L^-1 (kept in the unused
-//                upper triangle).
+//                singular rule, unit-diagonal scaling, chol_lower (mff_gram.h), the two
+//                triangular solves and diag(M^-1) from chol_inv_column.
 //   k_xr_residual, k_xr_mean: elementwise / per-factor day loops.
 // Every sum has one fixed order, so results are bit-identical from run to run.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mff.h"
+#include "mff_gram.h"
 #include "mff_internal.h"
 #include "mff_wave.h"
 
@@ -40,20 +33,9 @@ namespace mff {
 
 constexpr int XR_MAX_K = 63;
 constexpr int XR_MAX_G = 256;
-constexpr int XR_B = 64;            // padded columns of the Gram block
-constexpr int XR_KT = 32;           // stocks per LDS tile
-constexpr int XR_STR = XR_KT + 2;   // row stride of the tile (doubles)
-constexpr int XR_THREADS = 256;
-constexpr int XR_NR = XR_B * XR_KT / XR_THREADS;  // rows per thread (8)
-constexpr int XR_RS = XR_THREADS / XR_KT;         // row step (8)
-constexpr int XR_NT = 10;           // tiles on or below the block diagonal
-constexpr int XR_LS = XR_B + 1;     // row stride of the solve's matrix
 constexpr int XR_GC = 4;            // virtual columns per wave in k_xr_groups
 constexpr double XR_CONST_REL = 1e-20;
-constexpr double XR_PIVOT_MIN = 1e-10;
 constexpr int XR_AGG = 6;
-
-typedef double xr_v4d __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline size_t xr_align(size_t b) { return (b + 255) & ~(size_t)255; }
 // workspace: dayinfo f64 [D][C + 4] | means f64 [D][Ge][C] | ugrp i32 [D][S]
@@ -65,8 +47,6 @@ __host__ __device__ inline size_t xr_ws_bytes(int K, int D, int S, int Ge) {
   return xr_ugrp_off(K, D, Ge) + xr_align((size_t)D * S * 4);
 }
 
-__device__ __forceinline__ bool xr_fin(double x, uint8_t s) { return s == MFF_STATE_VALUE && __builtin_isfinite(x); }
-
 __global__ __launch_bounds__(256) void k_xr_mask(const double* __restrict__ xv, const uint8_t* __restrict__ xs, int K,
                                                  int D, int S, const double* __restrict__ yv,
                                                  const uint8_t* __restrict__ ys, const double* __restrict__ wv,
@@ -76,10 +56,10 @@ __global__ __launch_bounds__(256) void k_xr_mask(const double* __restrict__ xv, 
   const int s = (int)blockIdx.y * 256 + (int)threadIdx.x;
   if (s >= S) return;
   const size_t ds = (size_t)d * S + s;
-  bool u = xr_fin(yv[ds], ys[ds]);
+  bool u = xs_usable(yv[ds], ys[ds]);
   if (wv) {
     const double w = wv[ds];
-    u = u && xr_fin(w, wst[ds]) && w > 0.0;
+    u = u && xs_usable(w, wst[ds]) && w > 0.0;
   }
   int32_t g = 0;
   if (group) {
@@ -88,7 +68,7 @@ __global__ __launch_bounds__(256) void k_xr_mask(const double* __restrict__ xv, 
   }
   for (int k = 0; k < K; ++k) {
     const size_t off = ((size_t)k * D + d) * (size_t)S + s;
-    u = u && xr_fin(xv[off], xs[off]);
+    u = u && xs_usable(xv[off], xs[off]);
   }
   ugrp[ds] = u ? g : -1;
 }
@@ -174,23 +154,23 @@ __global__ __launch_bounds__(256) void k_xr_groups(const double* __restrict__ xv
 // of an LDS table [Ge][C + 2] -- no reduction across lanes at all, one order.
 constexpr int XR_COL_G = 64;
 constexpr int XR_COL_T = 256;
-constexpr int XR_COL_STR = XR_KT + 1;
+constexpr int XR_COL_STR = GR_KT + 1;
 __global__ __launch_bounds__(XR_COL_T) void k_xr_groups_col(const double* __restrict__ xv, int K, int D, int S,
                                                             const double* __restrict__ yv,
                                                             const double* __restrict__ wv,
                                                             const int32_t* __restrict__ ugrp, int Ge, int split_stocks,
                                                             double* __restrict__ gsums) {
   __shared__ double tab[XR_COL_G * (XR_MAX_K + 3)];
-  __shared__ double tile[XR_B * XR_COL_STR];
-  __shared__ double wl[XR_KT];
-  __shared__ int gl[XR_KT];
+  __shared__ double tile[GR_B * XR_COL_STR];
+  __shared__ double wl[GR_KT];
+  __shared__ int gl[GR_KT];
   const int d = blockIdx.x, p = blockIdx.y, t = threadIdx.x;
   const int C = K + 1, CV = C + 2;
   const int sbeg = (int)min((long long)p * split_stocks, (long long)S);
   const int send = (int)min((long long)sbeg + split_stocks, (long long)S);
   for (int i = t; i < Ge * CV; i += XR_COL_T) tab[i] = 0.0;
-  const int ls = t & (XR_KT - 1), r0 = t / XR_KT;
-  double cv[XR_NR], wt = 0.0, sq = 0.0;
+  const int ls = t & (GR_KT - 1), r0 = t / GR_KT;
+  double cv[GR_NR], wt = 0.0, sq = 0.0;
   int g = -1;
   auto load = [&](int k0) {
     const int s = k0 + ls;
@@ -198,25 +178,25 @@ __global__ __launch_bounds__(XR_COL_T) void k_xr_groups_col(const double* __rest
     g = s < send ? ugrp[ds] : -1;
     wt = g >= 0 ? (wv ? wv[ds] : 1.0) : 0.0;
 #pragma unroll
-    for (int i = 0; i < XR_NR; ++i) {
-      const int r = r0 + XR_RS * i;
+    for (int i = 0; i < GR_NR; ++i) {
+      const int r = r0 + GR_RS * i;
       cv[i] = (g >= 0 && r <= K) ? (r < K ? xv[((size_t)r * D + d) * (size_t)S + s] : yv[ds]) : 0.0;
     }
   };
   if (sbeg < send) load(sbeg);
-  for (int k0 = sbeg; k0 < send; k0 += XR_KT) {
+  for (int k0 = sbeg; k0 < send; k0 += GR_KT) {
     __syncthreads();  // the previous tile's walk is done (first pass: tab is zeroed)
 #pragma unroll
-    for (int i = 0; i < XR_NR; ++i) tile[(r0 + XR_RS * i) * XR_COL_STR + ls] = cv[i];
-    if (t < XR_KT) {
+    for (int i = 0; i < GR_NR; ++i) tile[(r0 + GR_RS * i) * XR_COL_STR + ls] = cv[i];
+    if (t < GR_KT) {
       wl[ls] = wt;
       gl[ls] = g;
     }
     __syncthreads();
-    if (k0 + XR_KT < send) load(k0 + XR_KT);
+    if (k0 + GR_KT < send) load(k0 + GR_KT);
     if (t < CV) {
 #pragma unroll 8
-      for (int s = 0; s < XR_KT; ++s) {
+      for (int s = 0; s < GR_KT; ++s) {
         const int gs = gl[s];
         if (gs < 0) continue;  // (uniform over the block)
         const double x = t < C ? tile[t * XR_COL_STR + s] : 1.0;
@@ -304,103 +284,46 @@ __global__ __launch_bounds__(256) void k_xr_means(const double* __restrict__ gs_
   }
 }
 
-// this thread's part of a [64 columns][XR_KT stocks] tile: stock t % XR_KT, columns t / XR_KT + 8 i,
+// this thread's part of a [64 columns][GR_KT stocks] tile: stock t % GR_KT, columns t / GR_KT + 8 i,
 // already centred (0 outside U, beyond `send` and in the padding columns); wt = the stock's weight
 __device__ __forceinline__ void xr_load(const double* __restrict__ xv, const double* __restrict__ yv,
                                         const double* __restrict__ wv, const int32_t* __restrict__ ugrp,
                                         const double* __restrict__ means, int K, int D, int d, int S, int send,
-                                        int Ge, int k0, double (&cv)[XR_NR], double& wt) {
-  const int s = k0 + (int)(threadIdx.x & (XR_KT - 1));
+                                        int Ge, int k0, double (&cv)[GR_NR], double& wt) {
+  const int s = k0 + (int)(threadIdx.x & (GR_KT - 1));
   const bool in = s < send;
   const size_t ds = (size_t)d * S + (in ? s : 0);
   const int g = in ? ugrp[ds] : -1;
   wt = g >= 0 ? (wv ? wv[ds] : 1.0) : 0.0;
   const double* mg = means + ((size_t)d * Ge + (g >= 0 ? g : 0)) * (K + 1);
 #pragma unroll
-  for (int i = 0; i < XR_NR; ++i) {
-    const int r = (int)(threadIdx.x / XR_KT) + XR_RS * i;
+  for (int i = 0; i < GR_NR; ++i) {
+    const int r = (int)(threadIdx.x / GR_KT) + GR_RS * i;
     double v = 0.0;
     if (g >= 0 && r <= K) v = (r < K ? xv[((size_t)r * D + d) * (size_t)S + s] : yv[ds]) - mg[r];
     cv[i] = v;
   }
 }
 
-// the 10 tiles (row, col) on or below the block diagonal
-__host__ __device__ constexpr int xr_tr(int i) { return i < 1 ? 0 : i < 3 ? 1 : i < 6 ? 2 : 3; }
-__host__ __device__ constexpr int xr_tc(int i) { return i < 1 ? 0 : i < 3 ? i - 1 : i < 6 ? i - 3 : i - 6; }
-
 // gram [P][D][C][C], plane of split p at p * D + d
-__global__ __launch_bounds__(XR_THREADS) void k_xr_gram(const double* __restrict__ xv, const double* __restrict__ yv,
+__global__ __launch_bounds__(GR_THREADS) void k_xr_gram(const double* __restrict__ xv, const double* __restrict__ yv,
                                                         const double* __restrict__ wv,
                                                         const int32_t* __restrict__ ugrp,
                                                         const double* __restrict__ means, int K, int D, int S, int Ge,
                                                         int split_stocks, double* __restrict__ gram) {
-  __shared__ double tile[XR_B * XR_STR];
-  __shared__ double wts[XR_KT];
-  __shared__ double red[XR_NT * 256];
+  __shared__ double tile[GR_B * GR_STR];
+  __shared__ double wts[GR_KT];
+  __shared__ double red[GR_NT * 256];
   const int d = blockIdx.x, p = blockIdx.y;
-  const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int C = K + 1, nt = (C + 15) / 16;
+  const int C = K + 1;
   const int sbeg = (int)min((long long)p * split_stocks, (long long)S);
   const int send = (int)min((long long)sbeg + split_stocks, (long long)S);
-  const int r = l & 15, kq = l >> 4;
-  double cv[XR_NR], wt;
-  xr_v4d acc[XR_NT];
-#pragma unroll
-  for (int i = 0; i < XR_NT; ++i) acc[i] = xr_v4d{0.0, 0.0, 0.0, 0.0};
-
-  if (sbeg < send) xr_load(xv, yv, wv, ugrp, means, K, D, d, S, send, Ge, sbeg, cv, wt);
-  for (int k0 = sbeg; k0 < send; k0 += XR_KT) {
-    __syncthreads();  // the previous tile's reads are done
-    {
-      const int ls = t & (XR_KT - 1);
-#pragma unroll
-      for (int i = 0; i < XR_NR; ++i) tile[((t / XR_KT) + XR_RS * i) * XR_STR + ls] = cv[i];
-      if (t < XR_KT) wts[ls] = wt;
-    }
-    __syncthreads();
-    if (k0 + XR_KT < send) xr_load(xv, yv, wv, ugrp, means, K, D, d, S, send, Ge, k0 + XR_KT, cv, wt);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int k = (2 * w + kk) * 4 + kq;
-      const double wk = wts[k];
-      double a[4], b[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        a[c] = tile[(16 * c + r) * XR_STR + k];
-        b[c] = a[c] * wk;
-      }
-#pragma unroll
-      for (int i = 0; i < XR_NT; ++i)
-        if (xr_tr(i) < nt) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[xr_tr(i)], b[xr_tc(i)], acc[i], 0, 0, 0);
-    }
-  }
-
-  for (int ww = 0; ww < 4; ++ww) {  // wave order
-    if (w == ww) {
-#pragma unroll
-      for (int i = 0; i < XR_NT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          double* e = &red[i * 256 + q * 64 + l];
-          *e = ww == 0 ? acc[i][q] : *e + acc[i][q];
-        }
-    }
-    __syncthreads();
-  }
-  double* out = gram + ((size_t)p * D + d) * (size_t)C * C;
-  for (int e = t; e < XR_NT * 256; e += XR_THREADS) {
-    const int ti = e >> 8, q = (e >> 6) & 3, ll = e & 63;
-    int tr = 0, tc = 0;
-    for (int i = 0; i < XR_NT; ++i)
-      if (i == ti) {
-        tr = xr_tr(i);
-        tc = xr_tc(i);
-      }
-    const int i = 16 * tr + (ll >> 4) + 4 * q, j = 16 * tc + (ll & 15);
-    if (i >= C || j > i) continue;
-    out[(size_t)i * C + j] = out[(size_t)j * C + i] = red[e];
-  }
+  gram_block<true>(
+      C, sbeg, send,
+      [&](int k0, double(&cv)[GR_NR], double& wt) {
+        xr_load(xv, yv, wv, ugrp, means, K, D, d, S, send, Ge, k0, cv, wt);
+      },
+      tile, wts, red, gram + ((size_t)p * D + d) * (size_t)C * C);
 }
 
 __global__ __launch_bounds__(WAVE) void k_xr_solve(const double* __restrict__ gram_all, int P, int K, int D,
@@ -408,9 +331,9 @@ __global__ __launch_bounds__(WAVE) void k_xr_solve(const double* __restrict__ gr
                                                    double* __restrict__ beta, double* __restrict__ tstat,
                                                    double* __restrict__ r2, int32_t* __restrict__ nout,
                                                    int32_t* __restrict__ dofout, int32_t* __restrict__ status) {
-  __shared__ double A[XR_B * XR_LS];
-  __shared__ double bb[XR_B];
-  __shared__ double sc[XR_B];
+  __shared__ double A[GR_B * GR_LS];
+  __shared__ double bb[GR_B];
+  __shared__ double sc[GR_B];
   __shared__ int flag;
   const int d = blockIdx.x, t = threadIdx.x;
   const int C = K + 1;
@@ -425,7 +348,7 @@ __global__ __launch_bounds__(WAVE) void k_xr_solve(const double* __restrict__ gr
       double s = 0.0;
       for (int p = 0; p < P; ++p) s += gram_all[((size_t)p * D + d) * plane + e];  // plane order
       const int i = e / C, j = e - i * C;
-      if (j < K && i < K) A[i * XR_LS + j] = s;
+      if (j < K && i < K) A[i * GR_LS + j] = s;
       if (j == K) bb[i] = s;  // bb[K] = T
     }
   }
@@ -435,7 +358,7 @@ __global__ __launch_bounds__(WAVE) void k_xr_solve(const double* __restrict__ gr
     T = bb[K];
     rawy = info[4 + K];
     if (t < K) {
-      const double mjj = A[t * XR_LS + t];
+      const double mjj = A[t * GR_LS + t];
       if (!(mjj > XR_CONST_REL * info[4 + t])) flag = 1;  // constant within industries (or not finite)
       sc[t] = 1.0 / sqrt(mjj);
     }
@@ -446,63 +369,32 @@ __global__ __launch_bounds__(WAVE) void k_xr_solve(const double* __restrict__ gr
   if (stat == 0) {
     for (int e = t; e < K * K; e += WAVE) {
       const int i = e / K, j = e - i * K;
-      A[i * XR_LS + j] *= sc[i] * sc[j];
+      A[i * GR_LS + j] *= sc[i] * sc[j];
     }
     if (t < K) bb[t] = yconst ? 0.0 : bb[t] * sc[t];
     __syncthreads();
-    // unpivoted Cholesky, row t on thread t, L in the lower triangle
-    for (int k = 0; k < K; ++k) {
-      const double piv = A[k * XR_LS + k];
-      if (!(piv > XR_PIVOT_MIN)) {  // (uniform: every thread reads the same entry)
-        stat = 2;
-        break;
-      }
-      const double lkk = sqrt(piv);
-      __syncthreads();
-      if (t == k) A[k * XR_LS + k] = lkk;
-      double lik = 0.0;
-      if (t > k && t < K) {
-        lik = A[t * XR_LS + k] / lkk;
-        A[t * XR_LS + k] = lik;
-      }
-      __syncthreads();
-      if (t > k && t < K)
-        for (int j = k + 1; j <= t; ++j) A[t * XR_LS + j] -= lik * A[j * XR_LS + k];
-      __syncthreads();
-    }
+    if (!chol_lower(A, K, t, CHOL_PIVOT_MIN)) stat = 2;
   }
   double bj = qnan(), tj = qnan(), r2v = qnan();
   if (stat == 0) {
     // L z = b, then L^T beta~ = z, both in bb
     for (int k = 0; k < K; ++k) {
-      const double zk = bb[k] / A[k * XR_LS + k];
+      const double zk = bb[k] / A[k * GR_LS + k];
       __syncthreads();
       if (t == k) bb[k] = zk;
-      if (t > k && t < K) bb[t] -= A[t * XR_LS + k] * zk;
+      if (t > k && t < K) bb[t] -= A[t * GR_LS + k] * zk;
       __syncthreads();
     }
     double zz = t < K ? bb[t] * bb[t] : 0.0;  // b^T beta = z^T z
     const double btb = wsum(zz);
     for (int k = K - 1; k >= 0; --k) {
-      const double xk = bb[k] / A[k * XR_LS + k];
+      const double xk = bb[k] / A[k * GR_LS + k];
       __syncthreads();
       if (t == k) bb[k] = xk;
-      if (t < k) bb[t] -= A[k * XR_LS + t] * xk;
+      if (t < k) bb[t] -= A[k * GR_LS + t] * xk;
       __syncthreads();
     }
-    // column t of L^-1 into row t of the upper triangle; (M~^-1)_tt = its squared norm
-    double inv = 0.0;
-    if (t < K) {
-      const double vt = 1.0 / A[t * XR_LS + t];
-      inv = vt * vt;
-      for (int i = t + 1; i < K; ++i) {
-        double s = A[i * XR_LS + t] * vt;
-        for (int k = t + 1; k < i; ++k) s += A[i * XR_LS + k] * A[t * XR_LS + k];
-        const double vi = -s / A[i * XR_LS + i];
-        A[t * XR_LS + i] = vi;
-        inv += vi * vi;
-      }
-    }
+    const double inv = chol_inv_column(A, K, t);  // (M~^-1)_tt
     const double Tz = yconst ? 0.0 : T;
     double rss = Tz - btb;
     if (!(rss > 0.0)) rss = 0.0;
@@ -629,10 +521,8 @@ __global__ __launch_bounds__(WAVE) void k_xr_mean(const double* __restrict__ bet
 }
 
 static int xr_check(const char* what, int K, int D, int S, int G) {
-  MFF_REQUIRE(K >= 1 && K <= XR_MAX_K, "%s: K=%d outside [1, %d]", what, K, XR_MAX_K);
-  MFF_REQUIRE(D >= 0 && S >= 0, "%s: bad sizes D=%d S=%d", what, D, S);
+  if (int rc = xs_check(what, K, XR_MAX_K, D, S)) return rc;
   MFF_REQUIRE(G >= 0 && G <= XR_MAX_G, "%s: G=%d outside [1, %d]", what, G, XR_MAX_G);
-  MFF_REQUIRE(S < (1 << 24) && (long long)D * S < (1ll << 40), "%s: panel too large", what);
   return 0;
 }
 
@@ -670,8 +560,7 @@ int mff_xs_reg_groups(const double* x_val, const uint8_t* x_state, int K, int D,
     MFF_LAUNCH_CHECK();
   }
   const int CV = K + 3;
-  const int tiles = (S + XR_KT - 1) / XR_KT;
-  const int split_stocks = max(1, (tiles + nsplit - 1) / nsplit) * XR_KT;
+  const int split_stocks = xs_split_stocks(S, nsplit);
   if (Ge <= XR_COL_G)
     hipLaunchKernelGGL(k_xr_groups_col, dim3((unsigned)D, (unsigned)nsplit), dim3(XR_COL_T), 0, st, x_val, K, D, S, y_val,
                        weight, ugrp, Ge, split_stocks, gsums);
@@ -698,10 +587,8 @@ int mff_xs_reg_gram(const double* x_val, int K, int D, int S, const double* y_va
   hipLaunchKernelGGL(k_xr_means, dim3((unsigned)D), dim3(256), 0, st, gsums_all, R, K, D, Ge,
                      G > 0 ? 0 : 1, means, dayinfo);
   MFF_LAUNCH_CHECK();
-  const int tiles = (S + XR_KT - 1) / XR_KT;
-  const int split_stocks = max(1, (tiles + nsplit - 1) / nsplit) * XR_KT;
-  hipLaunchKernelGGL(k_xr_gram, dim3((unsigned)D, (unsigned)nsplit), dim3(XR_THREADS), 0, st, x_val, y_val, weight, ugrp,
-                     means, K, D, S, Ge, split_stocks, gram);
+  hipLaunchKernelGGL(k_xr_gram, dim3((unsigned)D, (unsigned)nsplit), dim3(GR_THREADS), 0, st, x_val, y_val, weight,
+                     ugrp, means, K, D, S, Ge, xs_split_stocks(S, nsplit), gram);
   MFF_LAUNCH_CHECK();
   return 0;
 }

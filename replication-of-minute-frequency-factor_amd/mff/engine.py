@@ -998,6 +998,44 @@ CORR_GATHER_BYTES = 256 << 20  # cap of the gathered sum planes of one day batch
 CORR_PLANE_BYTES = 4 << 30     # cap of the sum planes of one day batch (single rank)
 
 
+def _int_arg(name: str, v, lo: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def _factor_rows(val: torch.Tensor, state: torch.Tensor, fn: str, kmax: int, names: str = "x_val and x_state",
+                 k: str = "K"):
+    """The [K][D][S] check of the factor_* entry points -> (val float64, state uint8), contiguous."""
+    if val.dim() != 3 or state.shape != val.shape:
+        raise ValueError(f"{names} must be [{k}][D][S]")
+    if val.shape[0] < 1 or val.shape[0] > kmax:
+        raise _lib.MffError(f"{fn}: {k}={val.shape[0]} outside [1, {kmax}]")
+    return val.to(torch.float64).contiguous(), state.to(torch.uint8).contiguous()
+
+
+def _nsplit(split: Optional[int], D: int, S: int, comm) -> int:
+    """Stock runs per day: ``split``, or :func:`reg_splits` (sharded: 1)."""
+    nsplit = int(split) if split is not None else (reg_splits(D, S) if comm is None else 1)
+    if nsplit < 1:
+        raise ValueError(f"split must be >= 1, got {split!r}")
+    return nsplit
+
+
+def _day_batches(D: int, day_bytes: int, R: int, sharded: bool):
+    """Day batches (d0, nd, whole) whose planes of ``day_bytes`` per day stay below
+    CORR_PLANE_BYTES, or below CORR_GATHER_BYTES once the R shards' planes are gathered."""
+    nd_max = max(1, (CORR_GATHER_BYTES // R if sharded else CORR_PLANE_BYTES) // day_bytes)
+    for d0 in range(0, D, nd_max):
+        nd = min(nd_max, D - d0)
+        yield d0, nd, nd == D
+
+
+def _days(t: Optional[torch.Tensor], d0: int, nd: int, whole: bool, dim: int = 0):
+    """Days [d0, d0 + nd) along ``dim`` of t, contiguous; t itself for None or the whole batch."""
+    return t if (t is None or whole) else t.narrow(dim, d0, nd).contiguous()
+
+
 def factor_corr(val: torch.Tensor, state: torch.Tensor, method: str = "pearson", min_pairs: int = 2,
                 comm=None, stocks_total: Optional[int] = None):
     """Per-day pairwise correlation of the exposure rows [F][D][S_loc] (mff_xs_corr_*; the
@@ -1018,20 +1056,14 @@ def factor_corr(val: torch.Tensor, state: torch.Tensor, method: str = "pearson",
     lib = _lib.load()
     if method not in CORR_METHODS:
         raise ValueError(f"method must be one of {CORR_METHODS}, got {method!r}")
-    if isinstance(min_pairs, bool) or not isinstance(min_pairs, (int, np.integer)) or min_pairs < 2:
-        raise ValueError(f"min_pairs must be an integer >= 2, got {min_pairs!r}")
-    if val.dim() != 3 or state.shape != val.shape:
-        raise ValueError("val and state must be [rows][D][S]")
+    min_pairs = _int_arg("min_pairs", min_pairs, 2)
+    val, state = _factor_rows(val, state, "factor_corr", lib.mff_xs_corr_max_rows(), "val and state", "rows")
     rows, D, S = val.shape
-    if rows < 1 or rows > lib.mff_xs_corr_max_rows():
-        raise _lib.MffError(f"factor_corr: rows={rows} outside [1, {lib.mff_xs_corr_max_rows()}]")
     dev = val.device
     st = _stream(dev)
-    val, state = val.to(torch.float64).contiguous(), state.to(torch.uint8).contiguous()
     if method == "spearman":
         masked = torch.where((state == VALUE) & ~torch.isfinite(val), torch.full_like(state, NULL), state)
         val, state = cross_section(val, masked, "rank", comm=comm, stocks_total=stocks_total)
-    min_pairs = int(min_pairs)
     corr = torch.empty((D, rows, rows), dtype=torch.float64, device=dev)
     n = torch.empty((D, rows, rows), dtype=torch.int32, device=dev)
     if D == 0:
@@ -1049,14 +1081,8 @@ def factor_corr(val: torch.Tensor, state: torch.Tensor, method: str = "pearson",
         center = torch.where(tot[..., 0] > 0, tot[..., 1] / tot[..., 0].clamp(min=1.0),
                              torch.zeros((), dtype=torch.float64, device=dev)).contiguous()
     ws = torch.empty(max(lib.mff_xs_corr_workspace_bytes(rows, D, S), 8), dtype=torch.uint8, device=dev)
-    day_bytes = 4 * rows * rows * 8
-    nd_max = max(1, (CORR_PLANE_BYTES if comm is None else CORR_GATHER_BYTES // R) // day_bytes)
-    for d0 in range(0, D, nd_max):
-        nd = min(nd_max, D - d0)
-        whole = nd == D
-        v = val if whole else val[:, d0:d0 + nd].contiguous()
-        s_ = state if whole else state[:, d0:d0 + nd].contiguous()
-        c = None if center is None else (center if whole else center[:, d0:d0 + nd].contiguous())
+    for d0, nd, whole in _day_batches(D, 4 * rows * rows * 8, R, comm is not None):
+        v, s_, c = _days(val, d0, nd, whole, 1), _days(state, d0, nd, whole, 1), _days(center, d0, nd, whole, 1)
         sums = torch.empty((nd, 4, rows, rows), dtype=torch.float64, device=dev)
         _lib.check(lib.mff_xs_corr_sums(_lib.ptr(v), _lib.ptr(s_), rows, nd, S, _lib.ptr(c), _lib.ptr(sums),
                                         _lib.ptr(ws), st), "mff_xs_corr_sums")
@@ -1130,13 +1156,9 @@ def factor_regress(x_val: torch.Tensor, x_state: torch.Tensor, y_val: torch.Tens
     planes are all-gathered in day batches (at most 256 MiB gathered at a time) and added in
     rank order; the residual is local; every rank returns the full per-day result."""
     lib = _lib.load()
-    if x_val.dim() != 3 or x_state.shape != x_val.shape:
-        raise ValueError("x_val and x_state must be [K][D][S]")
+    x_val, x_state = _factor_rows(x_val, x_state, "factor_regress", lib.mff_xs_reg_max_factors())
     K, D, S = x_val.shape
-    if K < 1 or K > lib.mff_xs_reg_max_factors():
-        raise _lib.MffError(f"factor_regress: K={K} outside [1, {lib.mff_xs_reg_max_factors()}]")
-    if isinstance(min_obs, bool) or not isinstance(min_obs, (int, np.integer)) or min_obs < 0:
-        raise ValueError(f"min_obs must be an integer >= 0, got {min_obs!r}")
+    min_obs = _int_arg("min_obs", min_obs, 0)
     if (weight is None) != (weight_state is None):
         raise ValueError("weight and weight_state go together")
     for name, t in (("y_val", y_val), ("y_state", y_state), ("weight", weight), ("weight_state", weight_state),
@@ -1146,7 +1168,6 @@ def factor_regress(x_val: torch.Tensor, x_state: torch.Tensor, y_val: torch.Tens
     dev = x_val.device
     st = _stream(dev)
     f64, u8 = torch.float64, torch.uint8
-    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
     y_val, y_state = y_val.to(f64).contiguous(), y_state.to(u8).contiguous()
     if weight is not None:
         weight, weight_state = weight.to(f64).contiguous(), weight_state.to(u8).contiguous()
@@ -1172,18 +1193,10 @@ def factor_regress(x_val: torch.Tensor, x_state: torch.Tensor, y_val: torch.Tens
     rv = torch.empty((D, S), dtype=f64, device=dev) if residual else None
     rs = torch.empty((D, S), dtype=u8, device=dev) if residual else None
     C = K + 1
-    nsplit = int(split) if split is not None else (reg_splits(D, S) if comm is None else 1)
-    if nsplit < 1:
-        raise ValueError(f"split must be >= 1, got {split!r}")
-    day_bytes = nsplit * C * C * 8
-    nd_max = max(1, (CORR_PLANE_BYTES if comm is None else CORR_GATHER_BYTES // R) // day_bytes)
-    for d0 in range(0, D, nd_max):
-        nd = min(nd_max, D - d0)
-        whole = nd == D
-        cut = lambda t_: t_ if (t_ is None or whole) else t_[d0:d0 + nd].contiguous()
-        xv = x_val if whole else x_val[:, d0:d0 + nd].contiguous()
-        xs = x_state if whole else x_state[:, d0:d0 + nd].contiguous()
-        yv, ys, wv, ws_, gp = cut(y_val), cut(y_state), cut(weight), cut(weight_state), cut(group)
+    nsplit = _nsplit(split, D, S, comm)
+    for d0, nd, whole in _day_batches(D, nsplit * C * C * 8, R, comm is not None):
+        xv, xs = _days(x_val, d0, nd, whole, 1), _days(x_state, d0, nd, whole, 1)
+        yv, ys, wv, ws_, gp = (_days(t_, d0, nd, whole) for t_ in (y_val, y_state, weight, weight_state, group))
         ws = torch.empty(max(lib.mff_xs_reg_workspace_bytes(K, nd, S, Gk), 8), dtype=u8, device=dev)
         gsums = torch.empty((nsplit, nd, Ge + 1, K + 3), dtype=f64, device=dev)
         _lib.check(lib.mff_xs_reg_groups(_lib.ptr(xv), _lib.ptr(xs), K, nd, S, _lib.ptr(yv), _lib.ptr(ys),
@@ -1194,7 +1207,7 @@ def factor_regress(x_val: torch.Tensor, x_state: torch.Tensor, y_val: torch.Tens
         _lib.check(lib.mff_xs_reg_gram(_lib.ptr(xv), K, nd, S, _lib.ptr(yv), _lib.ptr(wv), Gk, _lib.ptr(gs_all),
                                        R * nsplit, nsplit, _lib.ptr(gram), _lib.ptr(ws), st), "mff_xs_reg_gram")
         gram_all = gram if comm is None else comm.all_gather(gram).contiguous()
-        _lib.check(lib.mff_xs_reg_solve(_lib.ptr(gram_all), R * nsplit, K, nd, int(min_obs), _lib.ptr(beta[d0:]),
+        _lib.check(lib.mff_xs_reg_solve(_lib.ptr(gram_all), R * nsplit, K, nd, min_obs, _lib.ptr(beta[d0:]),
                                         _lib.ptr(tstat[d0:]), _lib.ptr(r2[d0:]), _lib.ptr(n[d0:]),
                                         _lib.ptr(dof[d0:]), _lib.ptr(status[d0:]), _lib.ptr(ws), st),
                    "mff_xs_reg_solve")
@@ -1252,19 +1265,14 @@ def factor_orthogonalize(x_val: torch.Tensor, x_state: torch.Tensor, method: str
     accepted for the call shape of :func:`factor_regress` and ignored: nothing here depends on
     the width of the other shards."""
     lib = _lib.load()
-    if x_val.dim() != 3 or x_state.shape != x_val.shape:
-        raise ValueError("x_val and x_state must be [K][D][S]")
+    x_val, x_state = _factor_rows(x_val, x_state, "factor_orthogonalize", lib.mff_xs_orth_max_factors())
     K, D, S = x_val.shape
-    if K < 1 or K > lib.mff_xs_orth_max_factors():
-        raise _lib.MffError(f"factor_orthogonalize: K={K} outside [1, {lib.mff_xs_orth_max_factors()}]")
     if method not in ORTH_METHODS:
         raise ValueError(f"method must be one of {ORTH_METHODS}, got {method!r}")
-    if isinstance(min_obs, bool) or not isinstance(min_obs, (int, np.integer)) or min_obs < 0:
-        raise ValueError(f"min_obs must be an integer >= 0, got {min_obs!r}")
+    min_obs = _int_arg("min_obs", min_obs, 0)
     dev = x_val.device
     st = _stream(dev)
     f64, u8 = torch.float64, torch.uint8
-    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
     R = 1 if comm is None else comm.world_size
     ov = torch.empty((K, D, S), dtype=f64, device=dev)
     os_ = torch.empty((K, D, S), dtype=u8, device=dev)
@@ -1273,17 +1281,10 @@ def factor_orthogonalize(x_val: torch.Tensor, x_state: torch.Tensor, method: str
     keep = torch.empty((D, K), dtype=f64, device=dev)
     n = torch.empty(D, dtype=torch.int32, device=dev)
     status = torch.empty(D, dtype=torch.int32, device=dev)
-    nsplit = int(split) if split is not None else (reg_splits(D, S) if comm is None else 1)
-    if nsplit < 1:
-        raise ValueError(f"split must be >= 1, got {split!r}")
+    nsplit = _nsplit(split, D, S, comm)
     m = ORTH_METHODS.index(method)
-    day_bytes = nsplit * K * K * 8
-    nd_max = max(1, (CORR_PLANE_BYTES if comm is None else CORR_GATHER_BYTES // R) // day_bytes)
-    for d0 in range(0, D, nd_max):
-        nd = min(nd_max, D - d0)
-        whole = nd == D
-        xv = x_val if whole else x_val[:, d0:d0 + nd].contiguous()
-        xs = x_state if whole else x_state[:, d0:d0 + nd].contiguous()
+    for d0, nd, whole in _day_batches(D, nsplit * K * K * 8, R, comm is not None):
+        xv, xs = _days(x_val, d0, nd, whole, 1), _days(x_state, d0, nd, whole, 1)
         bv = ov if whole else torch.empty((K, nd, S), dtype=f64, device=dev)
         bs = os_ if whole else torch.empty((K, nd, S), dtype=u8, device=dev)
         ws = torch.empty(max(lib.mff_xs_orth_workspace_bytes(K, nd, S), 8), dtype=u8, device=dev)
@@ -1295,7 +1296,7 @@ def factor_orthogonalize(x_val: torch.Tensor, x_state: torch.Tensor, method: str
         _lib.check(lib.mff_xs_orth_gram(_lib.ptr(xv), K, nd, S, _lib.ptr(sums_all), R * nsplit, nsplit,
                                         _lib.ptr(gram), _lib.ptr(ws), st), "mff_xs_orth_gram")
         gram_all = gram if comm is None else comm.all_gather(gram).contiguous()
-        _lib.check(lib.mff_xs_orth_solve(_lib.ptr(gram_all), R * nsplit, K, nd, m, int(min_obs), _lib.ptr(tr[d0:]),
+        _lib.check(lib.mff_xs_orth_solve(_lib.ptr(gram_all), R * nsplit, K, nd, m, min_obs, _lib.ptr(tr[d0:]),
                                          _lib.ptr(eig[d0:]), _lib.ptr(keep[d0:]), _lib.ptr(n[d0:]),
                                          _lib.ptr(status[d0:]), _lib.ptr(ws), st), "mff_xs_orth_solve")
         _lib.check(lib.mff_xs_orth_apply(_lib.ptr(xv), _lib.ptr(xs), K, nd, S, _lib.ptr(status[d0:]), _lib.ptr(bv),
@@ -1320,12 +1321,6 @@ class CombineResult(NamedTuple):
     n_pairs: torch.Tensor  # int32 [K][D]
     count: torch.Tensor    # int32 [D][K]: usable window dates behind each weight
     status: torch.Tensor   # int32 [D]: 0 ok, 1 too little history, 2 singular or degenerate
-
-
-def _int_arg(name: str, v, lo: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
-    return int(v)
 
 
 def _comb_moments(lib, xv, xs, yv, ys, Ky, min_obs, comm, st):
@@ -1367,11 +1362,8 @@ def factor_combine(x_val: torch.Tensor, x_state: torch.Tensor, y_val: Optional[t
     Stock-sharded (``comm``): the moment partials are all-gathered and merged in rank order,
     the weights are computed on every rank, the apply pass is local."""
     lib = _lib.load()
-    if x_val.dim() != 3 or x_state.shape != x_val.shape:
-        raise ValueError("x_val and x_state must be [K][D][S]")
+    x_val, x_state = _factor_rows(x_val, x_state, "factor_combine", COMBINE_MAX_FACTORS)
     K, D, S = x_val.shape
-    if K < 1 or K > COMBINE_MAX_FACTORS:
-        raise _lib.MffError(f"factor_combine: K={K} outside [1, {COMBINE_MAX_FACTORS}]")
     if method not in COMBINE_METHODS:
         raise ValueError(f"method must be one of {COMBINE_METHODS}, got {method!r}")
     if ic not in COMBINE_IC:
@@ -1395,7 +1387,6 @@ def factor_combine(x_val: torch.Tensor, x_state: torch.Tensor, y_val: Optional[t
     dev = x_val.device
     st = _stream(dev)
     f64, u8 = torch.float64, torch.uint8
-    x_val, x_state = x_val.to(f64).contiguous(), x_state.to(u8).contiguous()
     if y_val is not None:
         y_val, y_state = y_val.to(f64).contiguous(), y_state.to(u8).contiguous()
     zmom, ics, npairs = _comb_moments(lib, x_val, x_state, y_val, y_state, 0 if y_val is None else 1, min_obs,
