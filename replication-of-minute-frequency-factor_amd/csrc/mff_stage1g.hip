@@ -928,8 +928,12 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
           lds_fence();
           const uint32_t Sv = (uint32_t)sumv;
           const double inv = 1.0 / sumv;
-          // level 0 (the highest close) is the member shift of the share moments
-          const double x0 = (double)lv[0] * inv;
+          // level 0 (the highest close) is the member shift of the share moments; the shift is
+          // taken on the integral volumes (exact in f64), so equal level volumes give exact
+          // zeros (C7) whatever the compiler fuses: V * inv - x0 contracted to
+          // fma(V, inv, -x0) left the rounding residual of x0 on every level, and 120 equal
+          // levels a doc_kurt of -5e17 where the rule says NaN
+          const double v0 = (double)lv[0];
           // doc_pdf: the first level whose cumulative share exceeds k/20 is the first with
           // 20*cum > k*Sv, i.e. cum > floor(k*Sv/20) (integers); an exact tie
           // 20*cum == k*Sv at a level (only when 20 | k*Sv) is left to the exact path.
@@ -940,7 +944,7 @@ __global__ __launch_bounds__(256, kGWaves) void k_stage1g(GArgs a) {
             // instruction touches 16 consecutive words per group
             for (int l = g; l < L; l += 16) {
               const uint32_t V = lv[l] - (l > 0 ? lv[l - 1] : 0u);
-              const double dd = (double)V * inv - x0, d2 = dd * dd;
+              const double dd = ((double)V - v0) * inv, d2 = dd * dd;
               s1 += dd; s2 += d2; s3 += d2 * dd; s4 += d2 * d2;
             }
           }

@@ -8,6 +8,10 @@ RTOL = 1e-6 is the north-star tolerance for f64 accumulation over fp32 bars.  AT
 absolute floor for outputs that are differences of nearly equal quantities (skewness of
 near-symmetric sets, correlations and sums near zero, products minus one), where both
 implementations legitimately differ by f64 rounding of the terms (~1e-16 x term size).
+
+The 23 factors of the cancelling stage-1 families (MOMR, MOMV, MOMH, CORR, OLS) are also held
+to derived per-entry f64 bounds against a long-double reference: tests/stage1_ref.py
+(tests/test_stage1_ref.py, tests/test_gpu_stage1_bounds.py).  The tolerances here stay as they are.
 """
 import numpy as np
 
